@@ -2,7 +2,16 @@
 for scenes/cornell.json at 800x800, depth 8, stream compaction on (BASELINE configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--pipeline fused|staged]
-                    [--shard pixels|samples] [--no-cpu-baseline] [--no-configs]
+                    [--shard pixels|samples] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-configs] [--no-api] [--no-spread]]
+
+A plain run does what the headline needs and no more: set up, W warm-up steps, K timed steps, the
+outputs (`--dump-outputs DIR`: the accumulated image the timed path leaves, DIR/image.npy with
+DIR/image_nonfinite.npy marking its NaN pixels, float32, see dump_outputs;
+the scene and the iteration numbers are fixed, so two runs with the same arguments trace the same
+paths) and the result line.  Every other measurement below (kernel durations and `roofline`,
+`kernels`, `pcie_ms_per_frame`, `api`, `configs`, `cpu_baseline`, and with N > 1 the `inproc`
+follow-up) runs only with `--full`; the `--no-*` switches take single parts out of a full run.
 
 A "step" is one pathtrace() frame's worth of work per GPU: one sample for every pixel, all
 bounces, accumulated into the HBM-resident image (the reference's per-frame 7.68 MB D->H copy is
@@ -21,8 +30,8 @@ framebuffers with one RCCL reduce.
 
 Timing: W untimed frames, then barrier + device sync, K steps, device sync + barrier; the MAX over
 ranks of the elapsed time; value = segments traced by all ranks / that time.  The timed frames run
-as the library runs them: one hipGraph per multi-frame pass, replayed back to back.  On one GPU the
-same frames are then replayed eagerly with HIP start/stop events on every kernel
+as the library runs them: one hipGraph per multi-frame pass, replayed back to back.  With `--full`,
+on one GPU the same frames are then replayed eagerly with HIP start/stop events on every kernel
 (hipExtLaunchKernel, on the library's stream): the dominant kernel's average launch duration for
 `roofline` (algorithmic bytes / duration).  Then, still on one GPU: `api` times single
 pt_trace() calls as main.cpp:463 makes them (F = 1, image copied to host memory every frame),
@@ -85,6 +94,13 @@ def parse():
     ap.add_argument("--res", default="", help="WxH override (configs[4]: 1600x1600)")
     ap.add_argument("--depth", type=int, default=-1, help="trace depth override (configs[4]: 12)")
     ap.add_argument("--variant", type=int, default=-1, help="kernel variant bits (A/B; default: the library's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure kernel durations / roofline, the per-pass spread, the "
+                         "image copy, the API-faithful frame, the configs[2..4] sub-records and the CPU baseline "
+                         "(N>1: rank 0's --inproc follow-up); off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed steps computed, the accumulated image as the caller receives "
+                         "it, to DIR/image.npy + DIR/image_nonfinite.npy (float32) after the last timed step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the configs[2..4] sub-records")
     ap.add_argument("--no-api", action="store_true", help="skip the single-frame pt_trace() timing")
@@ -124,6 +140,24 @@ def shard_rows(height: int, world: int) -> int:
     return 1
 
 
+def dump_outputs(directory, tr):
+    """`--dump-outputs DIR`: the arrays a caller of the timed path receives after its last step,
+    one DIR/<name>.npy each.  The path's one output is the accumulated image (width*height x 3
+    float32, 7.68 MB at 800x800).  Like the reference, the tracer leaves a few pixels NaN (cornell:
+    3 of 640,000), and NaN compares unequal to itself, so the image is written as two arrays that
+    any comparison can take: image.npy with every non-finite component set to 0, and
+    image_nonfinite.npy (float32, same shape) holding 0 for a finite component, 1 for NaN, 2 for
+    +inf, 3 for -inf.  Together they are the caller's image, bit for bit but for NaN payloads."""
+    os.makedirs(directory, exist_ok=True)
+    img = np.ascontiguousarray(tr.image(), dtype=np.float32)
+    code = np.zeros(img.shape, np.float32)
+    code[np.isnan(img)] = 1.0
+    code[np.isposinf(img)] = 2.0
+    code[np.isneginf(img)] = 3.0
+    np.save(os.path.join(directory, "image.npy"), np.where(code > 0, np.float32(0), img))
+    np.save(os.path.join(directory, "image_nonfinite.npy"), code)
+
+
 def inproc_main(args):
     """`--gpus N --inproc`: one process, one PathTracer over N devices (pt_options.num_devices),
     every frame split into interleaved row bands across them and combined into device 0's image
@@ -152,7 +186,9 @@ def inproc_main(args):
     it += args.steps * per_step
     st = tr.stats()
     assert st["frames_total"] == args.steps * per_step
-    # the API call (one frame per pathtrace(), image copied to host), as main.cpp:463 makes it: each
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr)
+    # --full: the API call (one frame per pathtrace(), image copied to host), as main.cpp:463 makes it: each
     # shard speculates its next frame and copies its own row bands over its own link; then the same
     # calls with the speculation off
     def api_calls(first):
@@ -164,18 +200,22 @@ def inproc_main(args):
                 ts.append(1e3 * (time.perf_counter() - t1))
         ts.sort()
         return round(ts[len(ts) // 2], 4)
-    api_ms = api_calls(it)
-    tr.set_speculation(False)
-    api_ms_nospec = api_calls(it + 25)
+    api_ms = api_ms_nospec = None
+    if args.full:
+        api_ms = api_calls(it)
+        tr.set_speculation(False)
+        api_ms_nospec = api_calls(it + 25)
     tr.free()
     out = {"metric": "Mpaths/s (rays x bounces / s), 800x800 cornell depth 8", "mode": "inproc",
            "value": round(st["segments_total"] / el / 1e6, 2), "unit": "Mpaths/s", "n_gpus": n,
            "devices": devices, "combine": args.combine, "steps": args.steps, "warmup": args.warmup,
            "frames_per_step": per_step, "ms_per_step": round(1e3 * el / args.steps, 4),
            "ms_per_frame": round(1e3 * el / (args.steps * per_step), 4),
-           "api_ms_per_frame": api_ms, "api_ms_per_frame_no_speculation": api_ms_nospec,
+           "higher_is_better": True, "dtype": "f32",
            "parallelism": f"one process, pt_options.num_devices={n}: interleaved 8-row bands per device, "
                           f"one combine into device 0 per call ({args.combine})"}
+    if args.full:
+        out.update({"api_ms_per_frame": api_ms, "api_ms_per_frame_no_speculation": api_ms_nospec})
     print(json.dumps(out), flush=True)
 
 
@@ -183,8 +223,8 @@ def inproc_child(args, world):
     """Rank 0 of a torchrun job, after the other ranks have exited: the same N GPUs once more, as
     ONE process behind one pathtrace() (--inproc), so the scaling run also times the path the
     reference's callers get.  A child process with a time limit: its failure is recorded, not fatal."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--inproc", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--scene", args.scene]
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--inproc", "--full", "--steps",
+           str(args.steps), "--warmup", str(args.warmup), "--scene", args.scene]
     # PT_BENCH_INPROC_DEVICES (e.g. "0,0"): the device list for a rehearsal with ranks sharing one GPU
     if os.environ.get("PT_BENCH_INPROC_DEVICES"):
         cmd += ["--inproc-devices", os.environ["PT_BENCH_INPROC_DEVICES"]]
@@ -291,8 +331,10 @@ def main():
     assert st["frames_total"] == args.steps * per_step, (st["frames_total"], args.steps, per_step)
     if args.dump_image and rank == 0:
         np.save(args.dump_image, tr.image())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr)
     prof = st_prof = spread = None
-    if world == 1:
+    if world == 1 and args.full:
         # kernel durations: the next K frames replayed eagerly with events around every kernel
         tr.reset_stats()
         gap = float(os.environ.get("PT_BENCH_PROF_GAP", "0"))
@@ -353,18 +395,19 @@ def main():
         if prof is not None:
             line["roofline"] = roofline(prof, st_prof, args.pipeline, args.steps, depth, headline)
             line["kernels"] = kernels_digest(prof, spread)
-        line["pcie_ms_per_frame"] = pcie_copy_ms(tr)
-        if world == 1 and not args.no_api:
+        if args.full:
+            line["pcie_ms_per_frame"] = pcie_copy_ms(tr)
+        if world == 1 and args.full and not args.no_api:
             line["api"] = api_frame_ms(tr, it + 3 * args.steps)
     tr.free()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_configs:
             line["configs"] = [sub_config(ptamd, c) for c in SUB_CONFIGS]
         if not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     if world > 1:
         dist.destroy_process_group()
-        if rank == 0 and not args.no_inproc and (backend == "nccl" or os.environ.get("PT_BENCH_INPROC_DEVICES")):
+        if rank == 0 and args.full and not args.no_inproc and (backend == "nccl" or os.environ.get("PT_BENCH_INPROC_DEVICES")):
             line["inproc"] = inproc_child(args, world)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -140,6 +140,41 @@ def test_bench_refuses_more_rccl_ranks_than_gpus():
     assert p.returncode == 2 and "RCCL ranks" in p.stderr, p.stderr[-400:]
 
 
+def test_bench_dump_outputs_marks_nonfinite(tmp_path):
+    """--dump-outputs: image.npy is finite everywhere, image_nonfinite.npy says which components
+    were NaN / +inf / -inf; together they give back the caller's image."""
+    sys.path.insert(0, os.path.dirname(PKG))
+    import bench
+    img = np.arange(30, dtype=np.float32).reshape(10, 3) / 7
+    img[1, 0], img[4, 2], img[9, 1], img[2, 1] = np.nan, np.inf, -np.inf, -0.0
+
+    class Tracer:
+        def image(self):
+            return img.copy()
+
+    out = tmp_path / "d" / "e"
+    bench.dump_outputs(str(out), Tracer())
+    assert sorted(os.listdir(out)) == ["image.npy", "image_nonfinite.npy"]
+    got, code = np.load(out / "image.npy"), np.load(out / "image_nonfinite.npy")
+    assert got.dtype == np.float32 and code.dtype == np.float32 and got.shape == code.shape == img.shape
+    assert np.isfinite(got).all()
+    assert code[1, 0] == 1 and code[4, 2] == 2 and code[9, 1] == 3 and code.sum() == 6
+    back = got.copy()
+    back[code == 1], back[code == 2], back[code == 3] = np.nan, np.inf, -np.inf
+    assert back.tobytes() == img.tobytes()
+
+
+def test_bench_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, os.path.dirname(PKG))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "x"
+
+
 def test_bench_sub_records_have_traffic_digests():
     """Every bench `configs` sub-record names a committed PMC digest (profiles/rNN_traffic_<tag>.json)
     with HBM bytes per frame for the kernels its roofline covers, so no record's `traffic` is null."""

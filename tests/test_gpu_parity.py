@@ -719,7 +719,7 @@ def test_bench_two_ranks_pixel_tiles(tmp_path, oracle):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup",
-                        "1", "--no-cpu-baseline", "--no-configs", "--no-api", "--dump-image", str(dump)],
+                        "1", "--full", "--no-cpu-baseline", "--no-configs", "--no-api", "--dump-image", str(dump)],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -735,6 +735,33 @@ def test_bench_two_ranks_pixel_tiles(tmp_path, oracle):
         r.trace(it)
     got = np.load(dump)
     assert _eq(got, r.image), int(np.sum(got.view(np.uint32) != r.image.view(np.uint32)))
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_image(tmp_path, oracle):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and reports only the headline
+    fields (everything else needs --full); `--dump-outputs DIR` writes the image those W + K frames
+    left: with its NaN pixels put back it equals the oracle's bit for bit."""
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--res", "96x80", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mpaths/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("roofline", "kernels", "pcie_ms_per_frame", "api", "configs", "cpu_baseline", "inproc"):
+        assert k not in line, k
+    assert sorted(os.listdir(out)) == ["image.npy", "image_nonfinite.npy"]
+    img, code = np.load(out / "image.npy"), np.load(out / "image_nonfinite.npy")
+    assert img.dtype == np.float32 and code.dtype == np.float32 and img.shape == code.shape == (96 * 80, 3)
+    assert np.isfinite(img).all() and set(np.unique(code)) <= {0.0, 1.0, 2.0, 3.0}
+    a = oracle.load_scene(scene_path("cornell"), res=(96, 80))
+    r = oracle.Renderer(a, oracle.options(**BIT))
+    for it in range(1, 2 + 3 + 1):
+        r.trace(it)
+    want = np.asarray(r.image, np.float32).reshape(-1, 3)
+    assert np.array_equal(code == 1, np.isnan(want)) and np.array_equal(code == 2, np.isposinf(want))
+    assert np.array_equal(code == 3, np.isneginf(want))
+    assert _eq(img[code == 0], want[code == 0])
 
 
 # ---- GPU BVH build (csrc/pt_bvh_build.hip) == scene.cpp:445-525, bit for bit ----

@@ -12,7 +12,7 @@ OUT=gpurun_out/ab_env_${AB_TAG:-x}.jsonl
 for r in $(seq "$ROUNDS"); do
   for arm in $AB_ENVS; do
     if [ "$arm" = "-" ]; then set --; else set -- $(echo "$arm" | tr ',' ' '); fi
-    line=$(env "$@" timeout -k 10 240 python bench.py --no-cpu-baseline --no-configs --no-api --no-spread \
+    line=$(env "$@" timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread \
            ${AB_ARGS:-} | tail -1) || { echo "bench failed for $arm"; exit 2; }
     echo "{\"round\": $r, \"arm\": \"$arm\", \"line\": $line}" >> "$OUT"
   done

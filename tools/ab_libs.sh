@@ -12,7 +12,7 @@ OUT=gpurun_out/ab_libs_${AB_TAG:-x}.jsonl
 : > "$OUT"
 for r in $(seq "$ROUNDS"); do
   for lib in $LIBS; do
-    line=$(PTAMD_LIB=$PWD/$lib timeout -k 10 240 python bench.py --no-cpu-baseline --no-configs --no-api --no-spread \
+    line=$(PTAMD_LIB=$PWD/$lib timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread \
            ${AB_ARGS:-} | tail -1) || { echo "bench failed for $lib"; exit 2; }
     echo "{\"round\": $r, \"lib\": \"$lib\", \"line\": $line}" >> "$OUT"
   done

@@ -7,9 +7,9 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
     -k "bnnuy or khaslana or phatphuck or textured" > gpurun_out/t_bvh.log 2>&1 || { tail -30 gpurun_out/t_bvh.log; exit 1; }
 tail -1 gpurun_out/t_bvh.log
 : > gpurun_out/bvh.jsonl
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 50 --warmup 8 --scene scenes/cornell_obj_bnnuy.json \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 50 --warmup 8 --scene scenes/cornell_obj_bnnuy.json \
     | tail -1 >> gpurun_out/bvh.jsonl || exit 2
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 16 --warmup 4 --scene scenes/cornell_obj_khaslana.json \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 16 --warmup 4 --scene scenes/cornell_obj_khaslana.json \
     --res 1600x1600 --depth 12 | tail -1 >> gpurun_out/bvh.jsonl || exit 3
 python3 - <<'PY'
 import json

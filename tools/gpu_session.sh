@@ -21,14 +21,14 @@ if [ "$MODE" = all ] || [ "$MODE" = tests ]; then
     step pytest_gpu 900 python -m pytest tests -m gpu -q -rf --timeout 300 -p no:cacheprovider
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-    step bench 600 python bench.py --steps 100 --warmup 10
-    step bench_staged 600 python bench.py --steps 100 --warmup 10 --pipeline staged --no-cpu-baseline
+    step bench 600 python bench.py --full --steps 100 --warmup 10
+    step bench_staged 600 python bench.py --full --steps 100 --warmup 10 --pipeline staged --no-cpu-baseline
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
     step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-        python bench.py --steps 100 --warmup 10 --no-cpu-baseline
+        python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline
     step rocprof_staged 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_staged" -o run --output-format csv -- \
-        python bench.py --steps 100 --warmup 10 --no-cpu-baseline --pipeline staged
+        python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --pipeline staged
 fi
 if [ "$MODE" = all ] || [ "$MODE" = pmc ]; then
     step pmc_fused 900 env PMC_TAG=fused_ bash tools/pmc.sh

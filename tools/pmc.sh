@@ -15,7 +15,7 @@ for set in "${SETARR[@]}"; do
     i=$((i+1))
     echo "== pass $i: $set"
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $set -d "$OUT/${PMC_TAG:-}p$i" -o run --output-format csv -- \
-        python bench.py --steps ${PMC_STEPS:-32} --warmup ${PMC_WARMUP:-8} --no-cpu-baseline --no-configs --no-api --no-spread "$@" > "$OUT/${PMC_TAG:-}p$i.log" 2>&1
+        python bench.py --full --steps ${PMC_STEPS:-32} --warmup ${PMC_WARMUP:-8} --no-cpu-baseline --no-configs --no-api --no-spread "$@" > "$OUT/${PMC_TAG:-}p$i.log" 2>&1
     rc=$?
     echo "rc=$rc"
     if [ $rc -ne 0 ]; then tail -20 "$OUT/${PMC_TAG:-}p$i.log"; exit $rc; fi

@@ -21,8 +21,8 @@ for s in "$@"; do
     case $s in
         new) step pytest_new 400 $PYT tests/test_multi_device.py tests/test_dropin.py -m gpu ;;
         gpu) step pytest_gpu 700 $PYT tests -m gpu ;;
-        bench) step bench_k20 300 python bench.py --steps 20 --warmup 5 ;;
-        bench100) step bench 300 python bench.py --steps 100 --warmup 10 ;;
+        bench) step bench_k20 300 python bench.py --full --steps 20 --warmup 5 ;;
+        bench100) step bench 300 python bench.py --full --steps 100 --warmup 10 ;;
         *) echo "unknown step $s"; exit 2 ;;
     esac
 done

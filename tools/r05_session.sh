@@ -26,11 +26,11 @@ for s in "$@"; do
         mesh) step pytest_mesh 600 $PYT tests/test_gpu_parity.py tests/test_ref_pins.py -m gpu -k "bnnuy or khaslana or bvh or mesh or candidate or config5 or intersections" ;;
         gpu) step pytest_gpu 900 $PYT tests -m gpu ;;
         smoke) step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) step bench_k20 400 python bench.py --steps 20 --warmup 5 ;;
-        benchq) step bench_q 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-api --no-spread ;;
+        bench) step bench_k20 400 python bench.py --full --steps 20 --warmup 5 ;;
+        benchq) step bench_q 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-api --no-spread ;;
         multi) step multi_probe 300 python tools/multi_probe.py 20 ;;
         multidirect) PT_MULTI_F1_DIRECT=1 step multi_probe_direct 300 python tools/multi_probe.py 20 ;;
-        inproc) step inproc 200 python bench.py --gpus 2 --inproc --inproc-devices 0,0 --steps 20 --warmup 5 ;;
+        inproc) step inproc 200 python bench.py --full --gpus 2 --inproc --inproc-devices 0,0 --steps 20 --warmup 5 ;;
         ab_*)   # ab_<tag>: AB_LIBS / AB_ROUNDS from the environment, scenes below
             tag=${s#ab_}
             B=project3-cuda-path-tracer-2025_amd/build/ab
@@ -41,7 +41,7 @@ for s in "$@"; do
         apicopy)
             step prof_api_copy 300 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/prof_api_copy -o run --output-format csv -- python tools/api_trace.py run copy
             python tools/api_trace.py overlap gpurun_out/prof_api_copy/run_kernel_trace.csv gpurun_out/prof_api_copy/run_memory_copy_trace.csv --out gpurun_out/api_copy_overlap.json ;;
-        benchapi) step bench_api 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-spread ;;
+        benchapi) step bench_api 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-spread ;;
         hist) step sec_bunny 300 python -u tools/section_times.py --scene cornell_obj_bnnuy --variant 190 --frames 16 --out gpurun_out/sec_bunny.json
             step sec_khaslana 300 python -u tools/section_times.py --scene cornell_obj_khaslana --res 1600x1600 --depth 12 --variant 190 --frames 8 --out gpurun_out/sec_khaslana.json ;;
         tailtest) step pytest_tail 400 $PYT tests/test_bvh_tail.py -m gpu ;;
@@ -49,7 +49,7 @@ for s in "$@"; do
         laneab) ARMS="${LANE_ARMS:-PT_BVH_TAIL_LANES=0 PT_BVH_TAIL_LANES=16 PT_BVH_TAIL_LANES=24 PT_BVH_TAIL_LANES=32}"
             AB_TAG=lane_bunny AB_ENVS="$ARMS" AB_ARGS="--scene scenes/cornell_obj_bnnuy.json" step ab_lane_bunny 900 bash tools/ab_env.sh
             AB_TAG=lane_khaslana AB_ENVS="$ARMS" AB_ARGS="--scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12" step ab_lane_khaslana 900 bash tools/ab_env.sh ;;
-        meshstats) B="python bench.py --no-cpu-baseline --no-configs --no-api --no-spread"
+        meshstats) B="python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread"
             step prof_c4_bunny 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c4_bunny -o run --output-format csv -- $B --steps 48 --warmup 4 --scene scenes/cornell_obj_bnnuy.json
             step prof_c5_khaslana 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_khaslana -o run --output-format csv -- $B --steps 32 --warmup 2 --scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12 ;;
         empty) step empty_probe 120 project3-cuda-path-tracer-2025_amd/build/empty_block_probe ;;

@@ -8,7 +8,7 @@ set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="python bench.py --no-cpu-baseline --no-configs --no-api --no-spread"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread"
 MODE=${1:-all}
 st() {   # st TAG ARGS...
     local tag=$1; shift

@@ -39,12 +39,12 @@ for s in "$@"; do
             done ;;
         khprof)   # khaslana's kernel stats, PMC traffic and sections at the current build
             rm -rf gpurun_out/prof_c5_khaslana gpurun_out/pmc/khtr_p*
-            step prof_c5_khaslana 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_khaslana -o run --output-format csv -- python bench.py --no-cpu-baseline --no-configs --no-api --no-spread --steps 32 --warmup 2 --scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12
+            step prof_c5_khaslana 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_c5_khaslana -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread --steps 32 --warmup 2 --scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12
             PMC_TAG=khtr_ PMC_STEPS=8 PMC_WARMUP=2 PMC_SETS="FETCH_SIZE;WRITE_SIZE" step pmc_khtr 400 bash tools/pmc.sh --scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12
             PT_SECTIONS_SKIP_CAMERA=1 step sec_khaslana 300 python -u tools/section_times.py --scene cornell_obj_khaslana --res 1600x1600 --depth 12 --variant 190 --frames 8 --out gpurun_out/sec_khaslana.json ;;
         cyrprof)   # the 262k stand-in's kernel stats, PMC traffic and sections at the current build
             rm -rf gpurun_out/prof_m262k_cyrene gpurun_out/pmc/cyr_p*
-            step prof_m262k_cyrene 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_m262k_cyrene -o run --output-format csv -- python bench.py --no-cpu-baseline --no-configs --no-api --no-spread --steps 24 --warmup 2 --scene scenes/cornell_obj_cyrene.json
+            step prof_m262k_cyrene 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m262k_cyrene -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread --steps 24 --warmup 2 --scene scenes/cornell_obj_cyrene.json
             PMC_TAG=cyr_ PMC_STEPS=16 PMC_WARMUP=2 PMC_SETS="FETCH_SIZE;WRITE_SIZE" step pmc_cyr 400 bash tools/pmc.sh --scene scenes/cornell_obj_cyrene.json
             step sec_cyrene 300 python -u tools/section_times.py --scene cornell_obj_cyrene --variant 190 --frames 16 --out gpurun_out/sec_cyrene.json ;;
         cfgpmc)   # PMC traffic of the sub-records that had none (bench.py traffic_file names)
@@ -66,8 +66,8 @@ for s in "$@"; do
         mesh) step pytest_mesh 600 $PYT tests/test_gpu_parity.py tests/test_ref_pins.py -m gpu -k "bnnuy or khaslana or bvh or mesh or candidate or config5 or intersections" ;;
         gpu) step pytest_gpu 900 $PYT tests -m gpu ;;
         smoke) step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) step bench_k20 400 python bench.py --steps 20 --warmup 5 ;;
-        benchq) step bench_q 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-api --no-spread ;;
+        bench) step bench_k20 400 python bench.py --full --steps 20 --warmup 5 ;;
+        benchq) step bench_q 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-api --no-spread ;;
         calib) step calib_plain 120 project3-cuda-path-tracer-2025_amd/build/fetch_calib
             step calib_pmc 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/calib -o run --output-format csv -- project3-cuda-path-tracer-2025_amd/build/fetch_calib
             step calib_pmc_hit 120 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d gpurun_out/calib_hit -o run --output-format csv -- project3-cuda-path-tracer-2025_amd/build/fetch_calib ;;
@@ -83,7 +83,7 @@ for s in "$@"; do
         bandprobe) step band_probe 200 python tools/band_copy_probe.py ;;
         multi) step multi_probe 300 python tools/multi_probe.py 20 ;;
         multidirect) PT_MULTI_F1_DIRECT=1 step multi_probe_direct 300 python tools/multi_probe.py 20 ;;
-        inproc) step inproc 200 python bench.py --gpus 2 --inproc --inproc-devices 0,0 --steps 20 --warmup 5 ;;
+        inproc) step inproc 200 python bench.py --full --gpus 2 --inproc --inproc-devices 0,0 --steps 20 --warmup 5 ;;
         ab_*)   # ab_<tag>: AB_LIBS / AB_ROUNDS from the environment, scenes below
             tag=${s#ab_}
             B=project3-cuda-path-tracer-2025_amd/build/ab
@@ -97,12 +97,12 @@ for s in "$@"; do
         apicopy)
             step prof_api_copy 300 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/prof_api_copy -o run --output-format csv -- python tools/api_trace.py run copy
             python tools/api_trace.py overlap gpurun_out/prof_api_copy/run_kernel_trace.csv gpurun_out/prof_api_copy/run_memory_copy_trace.csv --out gpurun_out/api_copy_overlap.json ;;
-        benchapi) step bench_api 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-spread ;;
+        benchapi) step bench_api 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-spread ;;
         hist) step sec_bunny 300 python -u tools/section_times.py --scene cornell_obj_bnnuy --variant 190 --frames 16 --out gpurun_out/sec_bunny.json
             step sec_khaslana 300 python -u tools/section_times.py --scene cornell_obj_khaslana --res 1600x1600 --depth 12 --variant 190 --frames 8 --out gpurun_out/sec_khaslana.json ;;
         large) step pytest_large 600 $PYT tests/test_large_mesh.py -m gpu ;;
         multitest) step pytest_multi 600 $PYT tests/test_multi_device.py tests/test_speculation.py tests/test_dropin.py -m gpu ;;
-        benchlarge) B="python bench.py --no-cpu-baseline --no-configs --no-api --no-spread"
+        benchlarge) B="python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread"
             step bench_cyrene 300 $B --steps 24 --warmup 2 --scene scenes/cornell_obj_cyrene.json
             step bench_cyrene_nodes 300 $B --steps 8 --warmup 1 --scene scenes/cornell_obj_cyrene.json --variant 250
             step bench_phainon 300 $B --steps 24 --warmup 2 --scene scenes/cornell_obj_phainon.json
@@ -112,7 +112,7 @@ for s in "$@"; do
         laneab) ARMS="${LANE_ARMS:-PT_BVH_TAIL_LANES=0 PT_BVH_TAIL_LANES=16 PT_BVH_TAIL_LANES=24 PT_BVH_TAIL_LANES=32}"
             AB_TAG=lane_bunny AB_ENVS="$ARMS" AB_ARGS="--scene scenes/cornell_obj_bnnuy.json" step ab_lane_bunny 900 bash tools/ab_env.sh
             AB_TAG=lane_khaslana AB_ENVS="$ARMS" AB_ARGS="--scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12" step ab_lane_khaslana 900 bash tools/ab_env.sh ;;
-        meshstats) B="python bench.py --no-cpu-baseline --no-configs --no-api --no-spread"
+        meshstats) B="python bench.py --full --no-cpu-baseline --no-configs --no-api --no-spread"
             step prof_c4_bunny 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c4_bunny -o run --output-format csv -- $B --steps 48 --warmup 4 --scene scenes/cornell_obj_bnnuy.json
             step prof_c5_khaslana 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_khaslana -o run --output-format csv -- $B --steps 32 --warmup 2 --scene scenes/cornell_obj_khaslana.json --res 1600x1600 --depth 12 ;;
         occab) ARMS="- PT_BVH_LDS_PAD=5120 PT_BVH_LDS_PAD=11264"

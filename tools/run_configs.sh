@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 : > "$OUT/configs.jsonl"
 run() {   # run TAG ARGS...
     local tag=$1; shift
-    timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/cfg_$tag.log" 2>&1
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/cfg_$tag.log" 2>&1
     local rc=$?
     if [ $rc -ne 0 ]; then echo "$tag rc=$rc"; tail -5 "$OUT/cfg_$tag.log"; exit $rc; fi
     tail -1 "$OUT/cfg_$tag.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); d['tag']='$tag'; print(json.dumps(d))" >> "$OUT/configs.jsonl"

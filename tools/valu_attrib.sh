@@ -12,7 +12,7 @@ for lib in ${VA_LIBS:-project3-cuda-path-tracer-2025_amd/build/ab/new.so project
     tag=$(basename "$lib" .so)
     PTAMD_LIB=$PWD/$lib timeout -k 10 120 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS \
         -d "$OUT/$tag" -o run --output-format csv -- \
-        python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-api --no-spread > "$OUT/$tag.log" 2>&1
+        python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-api --no-spread > "$OUT/$tag.log" 2>&1
     rc=$?
     echo "$tag rc=$rc"
     if [ $rc -ne 0 ]; then tail -20 "$OUT/$tag.log"; exit $rc; fi
