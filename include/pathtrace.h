@@ -16,3 +16,9 @@ void pathtrace(uchar4* pbo, int frame, int iteration);
 // (ERRORCHECK / STREAM_COMPACTION / MATERIAL_SORTING / BVH_ACCELERATION, pathtrace.cu:20-24).
 // Takes effect at the next pathtraceInit.
 void pathtraceSetOptions(const pt_options& opts);
+
+// Framework addition: the accumulated image of the pathtrace() calls so far, divided by their
+// count and passed through the edge-avoiding a-trous filter of pt/pt_denoise.h with its default
+// parameters (feature buffer captured at iteration 1) -> out[width * height * 3].  The accumulated
+// image itself is untouched.
+void pathtraceDenoise(float* out);

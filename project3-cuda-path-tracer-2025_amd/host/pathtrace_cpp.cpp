@@ -3,10 +3,12 @@
 #include <cstdlib>
 
 #include "pathtrace.h"
+#include "pt/pt_denoise.h"
 
 namespace {
 Scene* hst_scene = nullptr;            // non-owning, like pathtrace.cu:82
 GuiDataContainer* guiData = nullptr;   // pathtrace.cu:83
+int last_iteration = 0;                // samples in the accumulated image (the last pathtrace call's iteration)
 pt_options g_opts;
 bool g_opts_set = false;
 
@@ -32,6 +34,7 @@ void pathtraceInit(Scene* scene) {
     if (!g_opts_set) pt_default_options(&g_opts);
     pt_scene_view v = scene->view();
     check(pt_init(&v, &g_opts), "pathtraceInit");
+    last_iteration = 0;
 }
 
 void pathtraceFree() { check(pt_free(), "pathtraceFree"); }
@@ -43,4 +46,12 @@ void pathtrace(uchar4* pbo, int frame, int iteration) {
     check(pt_set_camera(&hst_scene->state.camera), "pathtrace camera");
     float* img = hst_scene->state.image.empty() ? nullptr : &hst_scene->state.image[0].x;
     check(pt_trace(pbo, frame, iteration, img), "pathtrace");
+    last_iteration = iteration;
+}
+
+void pathtraceDenoise(float* out) {
+    if (!hst_scene || last_iteration < 1) check(PT_E_STATE, "pathtraceDenoise before pathtrace");
+    check(pt_set_camera(&hst_scene->state.camera), "pathtraceDenoise camera");
+    check(pt_gbuffer_capture(1), "pathtraceDenoise feature buffer");
+    check(pt_denoise(nullptr, last_iteration, nullptr, out), "pathtraceDenoise");
 }

@@ -8,7 +8,11 @@
 //             [--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh]
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
+//             [--denoise [LEVELS]]
 //
+// --denoise writes PREFIX.denoised.png beside the ordinary output: the averaged image through the
+// edge-avoiding a-trous filter of include/pt/pt_denoise.h (LEVELS passes, 1..8, default 5), saved
+// like saveImage with one sample.  The ordinary files are the same with or without it.
 // --events replays a recorded window session through the viewer state machine of
 // include/pt/pt_viewer.h (main.cpp's GLFW callbacks + runCuda) instead of rendering --spp frames.
 // One event per line ('#' starts a comment):
@@ -30,6 +34,7 @@
 
 #include "image_io.h"
 #include "pathtrace.h"
+#include "pt/pt_denoise.h"
 #include "pt/pt_viewer.h"
 
 static int run_events(const std::string& scene_file, const pt_options& opts, int resx, int resy, int depth,
@@ -111,12 +116,13 @@ int main(int argc, char** argv) {
         std::printf("Usage: %s SCENEFILE.json [--spp N] [--res WxH] [--depth D] [--out PREFIX] "
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
-                    "[--events FILE [--img-dir DIR] [--time-tag TAG]]\n", argv[0]);
+                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
     bool gpu_bvh = false;
     int spp = -1, resx = 0, resy = 0, depth = -1;
+    int denoise_levels = 0;   // 0: no --denoise
     pt_options opts;
     pt_default_options(&opts);
     for (int i = 2; i < argc; ++i) {
@@ -159,6 +165,22 @@ int main(int argc, char** argv) {
         else if (a == "--events") events = next();
         else if (a == "--img-dir") img_dir = next();
         else if (a == "--time-tag") time_tag = next();
+        else if (a == "--denoise") {   // the level count is optional: the next argument unless it is an option
+            pt_denoise_params dp;
+            pt_denoise_default_params(&dp);
+            denoise_levels = dp.levels;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* v = argv[++i];
+                char* end = nullptr;
+                const long n = std::strtol(v, &end, 10);
+                if (end == v || *end != '\0' || n < 1 || n > PT_DENOISE_MAX_LEVELS) {
+                    std::fprintf(stderr, "usage: --denoise [LEVELS], LEVELS an integer 1..%d, got '%s'\n",
+                                 PT_DENOISE_MAX_LEVELS, v);
+                    return 2;
+                }
+                denoise_levels = (int)n;
+            }
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (!events.empty()) return run_events(scene_file, opts, resx, resy, depth, events, img_dir, time_tag);
@@ -188,6 +210,19 @@ int main(int argc, char** argv) {
     std::vector<unsigned char> rgb = ptio::to_rgb8(scene->state.image, width, height, (float)iterations);
     bool ok = ptio::write_png(out + ".png", rgb, width, height) && ptio::write_pfm(out + ".pfm", scene->state.image, width, height);
     std::printf("Saved %s.png / %s.pfm\n", out.c_str(), out.c_str());
+    if (denoise_levels > 0 && ok) {   // after the last iteration: first hits of iteration 1, then the filter
+        pt_denoise_params dp;
+        pt_denoise_default_params(&dp);
+        dp.levels = denoise_levels;
+        std::vector<pt_vec3> den((size_t)width * height);
+        if (pt_gbuffer_capture(1) != PT_OK || pt_denoise(&dp, iterations, nullptr, &den[0].x) != PT_OK) {
+            std::fprintf(stderr, "--denoise: %s\n", pt_last_error());
+            ok = false;
+        } else {
+            ok = ptio::write_png(out + ".denoised.png", ptio::to_rgb8(den, width, height, 1.0f), width, height);
+            std::printf("Saved %s.denoised.png (%d levels)\n", out.c_str(), denoise_levels);
+        }
+    }
     pathtraceFree();
     delete scene;
     return ok ? 0 : 1;

@@ -107,6 +107,11 @@ VIEWER_SYMBOLS = [
     "pt_viewer_update_camera", "pt_viewer_run_frame", "pt_viewer_display", "pt_viewer_title", "pt_viewer_get_state",
     "pt_viewer_save_image", "pt_viewer_last_error",
 ]
+# include/pt/pt_denoise.h (first-hit feature buffer + edge-avoiding a-trous filter)
+DENOISE_SYMBOLS = [
+    "pt_denoise_default_params", "pt_gbuffer_capture", "pt_gbuffer_get", "pt_denoise", "pt_debug_denoise_timing",
+    "pt_debug_denoise_times",
+]
 
 
 def _load():
@@ -145,6 +150,9 @@ def _load():
         "pt_viewer_run_frame": (i32, [vp, vp]), "pt_viewer_display": (i32, [vp, vp, i64]),
         "pt_viewer_title": (i32, [vp, ctypes.c_char_p, i32]), "pt_viewer_get_state": (i32, [vp, vp]),
         "pt_viewer_save_image": (i32, [vp, ctypes.c_char_p, i32]), "pt_viewer_last_error": (ctypes.c_char_p, []),
+        "pt_denoise_default_params": (None, [vp]), "pt_gbuffer_capture": (i32, [i32]),
+        "pt_gbuffer_get": (i32, [vp, vp, vp, i64]), "pt_denoise": (i32, [vp, i32, vp, vp]),
+        "pt_debug_denoise_timing": (i32, [i32]), "pt_debug_denoise_times": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -197,6 +205,23 @@ def load_texture(path: str) -> np.ndarray:
     _check(lib.pt_texture_load(path.encode(), ctypes.byref(w), ctypes.byref(h), out.ctypes.data, out.size),
            "pt_texture_load")
     return out
+
+
+class _DenoiseParams(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int32), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_position", ctypes.c_float), ("demodulate_albedo", ctypes.c_int32)]
+
+
+def denoise_default_params(**kw) -> _DenoiseParams:
+    """pt_denoise_params with overrides (levels, sigma_color, sigma_normal, sigma_position,
+    demodulate_albedo)."""
+    p = _DenoiseParams()
+    lib.pt_denoise_default_params(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(_DenoiseParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, v)
+    return p
 
 
 class _TextureC(ctypes.Structure):
@@ -413,6 +438,24 @@ class PathTracer:
         out["n_sup"] = int(buf[len(self.SECTIONS) + 52])
         out["n_sup_wmax"] = int(buf[len(self.SECTIONS) + 53])
         out["n_sup_wunion"] = int(buf[len(self.SECTIONS) + 54])
+        return out
+
+    # ---- denoiser (include/pt/pt_denoise.h) ----
+    def capture_gbuffer(self, iteration: int = 1) -> dict:
+        """First hit of generateRayFromCamera(iteration) per pixel: {"normal_t", "position",
+        "albedo_mat"}, each (h, w, 4) float32 (see pt_gbuffer_get)."""
+        _check(lib.pt_gbuffer_capture(int(iteration)), "pt_gbuffer_capture")
+        out = {k: np.empty((self.height, self.width, 4), np.float32) for k in ("normal_t", "position", "albedo_mat")}
+        _check(lib.pt_gbuffer_get(out["normal_t"].ctypes.data, out["position"].ctypes.data,
+                                  out["albedo_mat"].ctypes.data, self.pixels), "pt_gbuffer_get")
+        return out
+
+    def denoise(self, samples: int, pbo_device_ptr: int | None = None, **params) -> np.ndarray:
+        """The accumulated image / samples through the a-trous filter, guided by the captured
+        feature buffer: (h, w, 3) float32.  The accumulated image is not written."""
+        p = denoise_default_params(**params)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        _check(lib.pt_denoise(ctypes.byref(p), int(samples), pbo_device_ptr, out.ctypes.data), "pt_denoise")
         return out
 
     # ---- single-kernel entry points (tests) ----
