@@ -22,3 +22,9 @@ void pathtraceSetOptions(const pt_options& opts);
 // parameters (feature buffer captured at iteration 1) -> out[width * height * 3].  The accumulated
 // image itself is untouched.
 void pathtraceDenoise(float* out);
+
+// Framework addition: the reference's NAIVE_MESH_LOADING switch (pathtrace.cu:365-393) at run time,
+// pt_set_naive_mesh of pt/pt_naive_mesh.h: every triangle in array order, no BVH.  Takes effect at
+// the next pathtraceInit; options set through pathtraceSetOptions must then ask for
+// PT_PIPELINE_STAGED (the defaults do).  The environment variable PT_NAIVE_MESH=1 does the same.
+void pathtraceSetNaiveMesh(bool enabled);

@@ -37,8 +37,10 @@
 
 #include "pt/pathtrace_abi.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_naive_mesh.h"
 #include "pt_kernels.h"
 #include "pt_denoise_kernels.h"
+#include "pt_naive_mesh_kernels.h"
 #include "trav_tree.h"
 
 using namespace ptd;
@@ -1240,6 +1242,8 @@ struct State {
     DevTriHot* d_hot4 = nullptr;
     float4* d_leaf9 = nullptr;
     DevTriCold* d_cold = nullptr;
+    bool naive = false;              // NAIVE_MESH_LOADING mode (pt/pt_naive_mesh.h): k_naive_mesh, no BVH
+    DevTriHot* d_naive_hot = nullptr;    // its triangle-ordered positions (allocated in that mode only)
     float4* d_path[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     float4* d_hit_nt = nullptr;
     int* d_hit_mat = nullptr;
@@ -1331,7 +1335,7 @@ int ctl_reset() {
 // execution time, independent of how far ahead of the GPU the host is.
 struct ProfRec {
     int kind;            // -1 frame begin, 0 camera, 1 intersect, 2 shade, 3 compact scatter,
-                         // 4 material sort, 5 compact count+scan, 100+b fused bounce b,
+                         // 4 material sort, 5 compact count+scan, 7 naive mesh loop, 100+b fused bounce b,
                          // 200+b its split BVH traversal kernel, 300+b k_tail from bounce b
     hipEvent_t start, stop;
 };
@@ -1586,6 +1590,10 @@ int enqueue_pass_body(int batch) {
             launch(1, k_intersect<true, false>, dim3(nb), dim3(BLOCK), gp->bvh_lds, gp->sc, pathbuf(cur), hits, n_in);
         else
             launch(1, k_intersect<false, false>, dim3(nb), dim3(BLOCK), 0, gp->sc, pathbuf(cur), hits, n_in);
+        // NAIVE_MESH_LOADING: every triangle in array order against the records just written
+        if (gp->naive && gp->sc.num_tris > 0)
+            launch(7, k_naive_mesh, dim3(nb), dim3(BLOCK), 0, gp->sc, (const DevTriHot*)gp->d_naive_hot, gp->sc.num_tris,
+                   pathbuf(cur), hits.nt, hits.mat, hits.uvd0, hits.uvd1, n_in);
         HIPCHK(hipGetLastError());
         const int* perm = nullptr;
         if (gp->opts.material_sort) {
@@ -2360,7 +2368,7 @@ void free_all() {
     for (hipEvent_t& e : gp->dn_ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     void* ptrs[] = {gp->d_geoms, gp->d_cull, gp->d_mats, gp->d_nodes, gp->d_node_aux, gp->d_hot, gp->d_pairs, gp->d_quads, gp->d_hot4,
-                    gp->d_leaf9, gp->d_cold, gp->d_texels, gp->d_texinfo, gp->d_image, gp->d_ctl, gp->d_grid};
+                    gp->d_leaf9, gp->d_cold, gp->d_naive_hot, gp->d_texels, gp->d_texinfo, gp->d_image, gp->d_ctl, gp->d_grid};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (gp->stream) (void)hipStreamDestroy(gp->stream);
@@ -2764,9 +2772,31 @@ int frame_depth_read() {
 // =============================================================================================
 // C-ABI
 // =============================================================================================
+// NAIVE_MESH_LOADING (pt/pt_naive_mesh.h): what the next pt_init uses; -1 until first asked, then
+// PT_NAIVE_MESH from the environment or what pt_set_naive_mesh stored
+static int g_naive_next = -1;
+static bool naive_next() {
+    if (g_naive_next < 0) {
+        const char* e = getenv("PT_NAIVE_MESH");
+        g_naive_next = (e && strtol(e, nullptr, 10) == 1) ? 1 : 0;
+    }
+    return g_naive_next != 0;
+}
+
 extern "C" {
 
 int32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+int32_t pt_set_naive_mesh(int32_t enabled) {
+    g_naive_next = enabled ? 1 : 0;
+    return PT_OK;
+}
+int32_t pt_get_naive_mesh(int32_t* next_init, int32_t* active) {
+    if (next_init) *next_init = naive_next() ? 1 : 0;
+    if (active) *active = (g_primary.inited && g_primary.naive) ? 1 : 0;
+    return PT_OK;
+}
+int32_t pt_debug_naive_mesh_tile(void) { return NAIVE_TILE; }
 const char* pt_last_error(void) { return g_err.c_str(); }
 
 void pt_default_options(pt_options* o) {
@@ -2775,7 +2805,9 @@ void pt_default_options(pt_options* o) {
     o->material_sort = 0;
     o->bvh = 1;
     o->arg_order = 0;
-    o->pipeline = PT_PIPELINE_FUSED;
+    // the naive mesh mode runs on the staged pipeline: with it on, that is the default, and a
+    // PT_PIPELINE_FUSED reaching pt_init is the caller's own choice (refused there)
+    o->pipeline = naive_next() ? PT_PIPELINE_STAGED : PT_PIPELINE_FUSED;
     o->use_graph = 1;
     o->device = 0;
     o->shard_mode = PT_SHARD_NONE;
@@ -2843,6 +2875,32 @@ int auto_batch(int local_pixels) {
     return f;
 }
 
+// cold triangle data by reference triangle index (vertex normals, uvs, tangents, material)
+static int32_t fill_cold(const pt_scene_view* s, std::vector<DevTriCold>& cold) {
+    cold.resize(s->num_triangles);
+    for (int i = 0; i < s->num_triangles; ++i) {
+        const pt_triangle& t = s->triangles[i];
+        DevTriCold& c = cold[i];
+        memset(&c, 0, sizeof c);
+        const pt_vertex* v[3] = {&t.v1, &t.v2, &t.v3};
+        float* ns[3] = {c.n0, c.n1, c.n2};
+        float* uvs[3] = {c.uv0, c.uv1, c.uv2};
+        for (int k = 0; k < 3; ++k) {
+            ns[k][0] = v[k]->normal.x;
+            ns[k][1] = v[k]->normal.y;
+            ns[k][2] = v[k]->normal.z;
+            uvs[k][0] = v[k]->uv.x;
+            uvs[k][1] = v[k]->uv.y;
+        }
+        c.dpdu[0] = t.dpdu.x; c.dpdu[1] = t.dpdu.y; c.dpdu[2] = t.dpdu.z;
+        c.dpdv[0] = t.dpdv.x; c.dpdv[1] = t.dpdv.y; c.dpdv[2] = t.dpdv.z;
+        c.materialID = t.materialID;
+        if (t.materialID < 0 || t.materialID >= std::max(1, s->num_materials))
+            return fail(PT_E_INVALID, "triangle %d material %d out of range", i, t.materialID);
+    }
+    return PT_OK;
+}
+
 // one context (gp): the whole pathtraceInit for one device, or for shard k of a multi-device
 // context; `share` contexts live on this device (auto F divides its free memory among them)
 static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
@@ -2853,6 +2911,14 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     if (s->num_geoms < 0 || s->num_materials < 0 || s->num_triangles < 0 || s->num_bvh_nodes < 0)
         return fail(PT_E_INVALID, "negative counts");
     if (s->num_materials > MAXMAT) return fail(PT_E_UNSUPPORTED, "more than %d materials", MAXMAT);
+    // NAIVE_MESH_LOADING (pt/pt_naive_mesh.h): staged pipeline, one unsharded context
+    const bool naive = naive_next();
+    if (naive && o.pipeline == PT_PIPELINE_FUSED)
+        return fail(PT_E_UNSUPPORTED, "naive mesh mode runs on the staged pipeline: pipeline = PT_PIPELINE_FUSED is not "
+                    "supported (take pt_default_options after pt_set_naive_mesh(1), or set PT_PIPELINE_STAGED)");
+    if (naive && o.shard_mode != PT_SHARD_NONE)
+        return fail(PT_E_UNSUPPORTED, "naive mesh mode: one unsharded device context only (shard_mode must be PT_SHARD_NONE)");
+    if (naive && s->num_triangles > 0 && !s->triangles) return fail(PT_E_INVALID, "triangles is NULL");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_E_NODEVICE, "no HIP device visible");
     if (o.device < 0 || o.device >= ndev) return fail(PT_E_INVALID, "device %d out of range", o.device);
@@ -3009,7 +3075,9 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     for (int i = 0; i < s->num_materials; ++i)
         if (s->materials[i].hasTexture || s->materials[i].hasBumpMap) gp->no_tex = false;
     // BVH: only when the reference would traverse it (BVH_ACCELERATION and a non-empty tree)
-    gp->has_bvh = o.bvh && s->num_bvh_nodes > 0 && s->num_triangles > 0;
+    // (the naive mesh mode skips it whatever the options and the scene view say)
+    gp->naive = naive;
+    gp->has_bvh = !naive && o.bvh && s->num_bvh_nodes > 0 && s->num_triangles > 0;
     std::vector<DevNode> nodes;
     std::vector<float4> node_aux;
     std::vector<DevTriHot> hot;
@@ -3131,27 +3199,7 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
             hot[k].b = make_float4(t.v2.position.y, t.v2.position.z, t.v3.position.x, t.v3.position.y);
             hot[k].c = make_float4(t.v3.position.z, fti, 0.f, 0.f);
         }
-        cold.resize(s->num_triangles);
-        for (int i = 0; i < s->num_triangles; ++i) {
-            const pt_triangle& t = s->triangles[i];
-            DevTriCold& c = cold[i];
-            memset(&c, 0, sizeof c);
-            const pt_vertex* v[3] = {&t.v1, &t.v2, &t.v3};
-            float* ns[3] = {c.n0, c.n1, c.n2};
-            float* uvs[3] = {c.uv0, c.uv1, c.uv2};
-            for (int k = 0; k < 3; ++k) {
-                ns[k][0] = v[k]->normal.x;
-                ns[k][1] = v[k]->normal.y;
-                ns[k][2] = v[k]->normal.z;
-                uvs[k][0] = v[k]->uv.x;
-                uvs[k][1] = v[k]->uv.y;
-            }
-            c.dpdu[0] = t.dpdu.x; c.dpdu[1] = t.dpdu.y; c.dpdu[2] = t.dpdu.z;
-            c.dpdv[0] = t.dpdv.x; c.dpdv[1] = t.dpdv.y; c.dpdv[2] = t.dpdv.z;
-            c.materialID = t.materialID;
-            if (t.materialID < 0 || t.materialID >= std::max(1, s->num_materials))
-                return fail(PT_E_INVALID, "triangle %d material %d out of range", i, t.materialID);
-        }
+        RC(fill_cold(s, cold));
         // traversal stack (LDS, MAXSTACK entries per lane at most).  The reference-order DFS needs
         // bvh_max_stack entries -- more than 64 overflows the reference's own int stack[64]
         // (intersections.cu:167), so such a tree is refused rather than traversed differently.
@@ -3386,6 +3434,21 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
         }
         gp->bvh_lds = (size_t)gp->stack_depth * BLOCK * sizeof(int);
     }
+    // naive mesh mode: the three positions of every triangle in ARRAY order (k_naive_mesh forms the
+    // edges tri_test() forms when it stages a tile), record k naming triangle k, and the cold data
+    std::vector<DevTriHot> naive_hot;
+    if (naive && s->num_triangles > 0) {
+        naive_hot.resize(s->num_triangles);
+        for (int k = 0; k < s->num_triangles; ++k) {
+            const pt_triangle& t = s->triangles[k];
+            float fk;
+            memcpy(&fk, &k, 4);
+            naive_hot[k].a = make_float4(t.v1.position.x, t.v1.position.y, t.v1.position.z, t.v2.position.x);
+            naive_hot[k].b = make_float4(t.v2.position.y, t.v2.position.z, t.v3.position.x, t.v3.position.y);
+            naive_hot[k].c = make_float4(t.v3.position.z, fk, 0.f, 0.f);
+        }
+        RC(fill_cold(s, cold));
+    }
     for (int i = 0; i < s->num_geoms; ++i)
         if (s->geoms[i].materialid < 0 || s->geoms[i].materialid >= std::max(1, s->num_materials))
             return fail(PT_E_INVALID, "geom %d material %d out of range", i, s->geoms[i].materialid);
@@ -3465,6 +3528,12 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
                 RC(upload(gp->d_quads, quads.data(), quads.size()));
             }
         }
+    }
+    if (!naive_hot.empty()) {
+        RC(dalloc(&gp->d_naive_hot, naive_hot.size()));
+        RC(upload(gp->d_naive_hot, naive_hot.data(), naive_hot.size()));
+        RC(dalloc(&gp->d_cold, cold.size()));
+        RC(upload(gp->d_cold, cold.data(), cold.size()));
     }
     // textures (pathtrace.cu:169-201): RGBA8 texels of every texture in one buffer
     int num_tex = 0;
@@ -3561,6 +3630,8 @@ int32_t pt_init(const pt_scene_view* s, const pt_options* opts_in) {
     else pt_default_options(&o);
     if (o.num_devices < 0 || o.num_devices > PT_MAX_DEVICES)
         return fail(PT_E_INVALID, "num_devices must be 0 .. %d", PT_MAX_DEVICES);
+    if (naive_next() && o.num_devices > 1)
+        return fail(PT_E_UNSUPPORTED, "naive mesh mode: one device context only (pt_options.num_devices > 1)");
     if (o.num_devices <= 1) {
         const int rc = init_one(s, o, 1);
         if (rc != PT_OK) free_all();   // whatever was allocated before the failure
@@ -3944,6 +4015,7 @@ void pt_denoise_default_params(pt_denoise_params* p) {
 
 int32_t pt_gbuffer_capture(int32_t iteration) {
     RC(denoise_ctx("pt_gbuffer_capture"));
+    if (gp->naive) return fail(PT_E_UNSUPPORTED, "pt_gbuffer_capture: not available in naive mesh mode");
     if (iteration <= 0) return fail(PT_E_INVALID, "iteration is 1-based, got %d", iteration);
     const int n = gp->pixels_total;
     gp->gbuf_valid = false;
@@ -4091,7 +4163,8 @@ int32_t pt_test_intersect(const pt_path_segment* paths, int64_t n, pt_shadeable_
         }
     } tmp;
     float4 *uvd0 = gp->d_hit_uvd0, *uvd1 = gp->d_hit_uvd1;
-    if (!uvd0 && gp->has_bvh) {
+    const bool naive_tris = gp->naive && gp->sc.num_tris > 0;
+    if (!uvd0 && (gp->has_bvh || naive_tris)) {
         RC(dalloc(&tmp.p[0], (size_t)n));
         RC(dalloc(&tmp.p[1], (size_t)n));
         uvd0 = tmp.p[0];
@@ -4107,6 +4180,10 @@ int32_t pt_test_intersect(const pt_path_segment* paths, int64_t n, pt_shadeable_
     else
         hipLaunchKernelGGL((k_intersect<false, false>), dim3(nblocks((int)n)), dim3(BLOCK), 0, gp->stream, gp->sc,
                            pathbuf(0), hits, staged_count(0));
+    if (naive_tris)   // as the staged pipeline runs it
+        hipLaunchKernelGGL(k_naive_mesh, dim3(nblocks((int)n)), dim3(BLOCK), 0, gp->stream, gp->sc,
+                           (const DevTriHot*)gp->d_naive_hot, gp->sc.num_tris, pathbuf(0), hits.nt, hits.mat, hits.uvd0,
+                           hits.uvd1, staged_count(0));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(gp->stream));
     std::vector<float4> nt(n);
@@ -4325,7 +4402,7 @@ int32_t pt_profile_frames(int32_t first_iteration, int32_t count, pt_kernel_time
         (void)hipEventElapsedTime(&frame_ms, e0, e1);
         for (int f = 0; f < passes; ++f) {
             size_t a = pass_start[f], b = (f + 1 < passes) ? pass_start[f + 1] : rec.size();
-            int bi = 0;
+            int bi = 0, ni = 0;
             for (size_t i = a; i < b; ++i) {
                 float ms = 0;
                 (void)hipEventElapsedTime(&ms, rec[i].start, rec[i].stop);
@@ -4341,6 +4418,7 @@ int32_t pt_profile_frames(int32_t first_iteration, int32_t count, pt_kernel_time
                 else if (k == 5) scan_ms += ms;
                 else if (k == 4) sort_ms += ms;
                 else if (k == 6) comb_ms += ms;
+                else if (k == 7) { isect_ms += ms; if (ni < MAXB) bvh_ms[ni++] += ms; }   // k_naive_mesh of bounce ni
             }
         }
     }

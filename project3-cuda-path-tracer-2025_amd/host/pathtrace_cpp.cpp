@@ -4,6 +4,7 @@
 
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_naive_mesh.h"
 
 namespace {
 Scene* hst_scene = nullptr;            // non-owning, like pathtrace.cu:82
@@ -23,6 +24,8 @@ void pathtraceSetOptions(const pt_options& opts) {
     g_opts = opts;
     g_opts_set = true;
 }
+
+void pathtraceSetNaiveMesh(bool enabled) { pt_set_naive_mesh(enabled ? 1 : 0); }
 
 void InitDataContainer(GuiDataContainer* imGuiData) {
     guiData = imGuiData;

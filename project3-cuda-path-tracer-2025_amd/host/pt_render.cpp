@@ -8,8 +8,10 @@
 //             [--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh]
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
-//             [--denoise [LEVELS]]
+//             [--denoise [LEVELS]] [--naive-mesh]
 //
+// --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
+// triangle in array order, no BVH.  It implies --pipeline staged.
 // --denoise writes PREFIX.denoised.png beside the ordinary output: the averaged image through the
 // edge-avoiding a-trous filter of include/pt/pt_denoise.h (LEVELS passes, 1..8, default 5), saved
 // like saveImage with one sample.  The ordinary files are the same with or without it.
@@ -116,11 +118,11 @@ int main(int argc, char** argv) {
         std::printf("Usage: %s SCENEFILE.json [--spp N] [--res WxH] [--depth D] [--out PREFIX] "
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
-                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]]\n", argv[0]);
+                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]] [--naive-mesh]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
-    bool gpu_bvh = false;
+    bool gpu_bvh = false, naive_mesh = false;
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
     pt_options opts;
@@ -141,6 +143,7 @@ int main(int argc, char** argv) {
         else if (a == "--no-bvh") opts.bvh = 0;
         else if (a == "--device") opts.device = std::atoi(next());
         else if (a == "--gpu-bvh") gpu_bvh = true;
+        else if (a == "--naive-mesh") naive_mesh = true;
         else if (a == "--devices") {   // every frame split into pixel shards over these GPUs
             const std::string d = next();
             opts.num_devices = 0;
@@ -182,6 +185,10 @@ int main(int argc, char** argv) {
             }
         }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (naive_mesh) {   // the mode runs on the staged pipeline
+        pathtraceSetNaiveMesh(true);
+        opts.pipeline = PT_PIPELINE_STAGED;
     }
     if (!events.empty()) return run_events(scene_file, opts, resx, resy, depth, events, img_dir, time_tag);
     Scene* scene = nullptr;

@@ -112,6 +112,8 @@ DENOISE_SYMBOLS = [
     "pt_denoise_default_params", "pt_gbuffer_capture", "pt_gbuffer_get", "pt_denoise", "pt_debug_denoise_timing",
     "pt_debug_denoise_times",
 ]
+# include/pt/pt_naive_mesh.h (the reference's NAIVE_MESH_LOADING mode)
+NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_mesh_tile"]
 
 
 def _load():
@@ -153,6 +155,7 @@ def _load():
         "pt_denoise_default_params": (None, [vp]), "pt_gbuffer_capture": (i32, [i32]),
         "pt_gbuffer_get": (i32, [vp, vp, vp, i64]), "pt_denoise": (i32, [vp, i32, vp, vp]),
         "pt_debug_denoise_timing": (i32, [i32]), "pt_debug_denoise_times": (i32, [vp, vp, vp]),
+        "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -193,6 +196,24 @@ def default_options(**kw) -> _Options:
             raise TypeError(f"unknown option {k}")
         setattr(o, k, int(v))
     return o
+
+
+def set_naive_mesh(enabled: bool):
+    """NAIVE_MESH_LOADING for the NEXT pt_init (include/pt/pt_naive_mesh.h): every triangle in array
+    order, no BVH; staged pipeline, one unsharded context.  Sticky until changed."""
+    _check(lib.pt_set_naive_mesh(int(bool(enabled))), "pt_set_naive_mesh")
+
+
+def get_naive_mesh() -> tuple:
+    """(what the next pt_init will use, what the live context was initialised with)."""
+    nxt, act = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_get_naive_mesh(ctypes.byref(nxt), ctypes.byref(act)), "pt_get_naive_mesh")
+    return bool(nxt.value), bool(act.value)
+
+
+def naive_mesh_tile() -> int:
+    """Triangles per LDS tile of k_naive_mesh (tests and tools)."""
+    return int(lib.pt_debug_naive_mesh_tile())
 
 
 def load_texture(path: str) -> np.ndarray:
@@ -323,16 +344,23 @@ class PathTracer:
 
     _live = None
 
-    def __init__(self, scene, **options):
+    def __init__(self, scene, naive_mesh: bool = False, **options):
+        """`naive_mesh=True`: the reference's NAIVE_MESH_LOADING mode for this tracer
+        (pt_set_naive_mesh around pt_init; the process-wide setting is put back afterwards)."""
         if PathTracer._live is not None:
             PathTracer._live.free()       # the library state is process-global, like the reference's
-        self.opts = default_options(**options)
-        view = scene.view() if hasattr(scene, "view") else scene
-        self.scene = scene
-        cam = np.frombuffer(bytes(view.camera), CAMERA)
-        self.width, self.height = int(cam["resolution"][0][0]), int(cam["resolution"][0][1])
-        self.trace_depth = int(view.trace_depth)
-        _check(lib.pt_init(ctypes.byref(view), ctypes.byref(self.opts)), "pt_init")
+        prev = get_naive_mesh()[0]
+        set_naive_mesh(naive_mesh)
+        try:
+            self.opts = default_options(**options)   # after the setter: staged by default in naive mode
+            view = scene.view() if hasattr(scene, "view") else scene
+            self.scene = scene
+            cam = np.frombuffer(bytes(view.camera), CAMERA)
+            self.width, self.height = int(cam["resolution"][0][0]), int(cam["resolution"][0][1])
+            self.trace_depth = int(view.trace_depth)
+            _check(lib.pt_init(ctypes.byref(view), ctypes.byref(self.opts)), "pt_init")
+        finally:
+            set_naive_mesh(prev)
         PathTracer._live = self
         self.iteration = 0
         self._host_image = None
