@@ -532,6 +532,78 @@ __global__ __launch_bounds__(BLOCK) void k_tail(SceneDev sc, PathBuf in, FrameCt
     }
 }
 
+// Bounces 0 and 1 of a primitive-only scene in ONE launch (PT_HEAD_FUSE, enqueue_pass_body): the
+// camera bounce as k_bounce<true, false, 18> runs it (per-lane nearest-first queue), then, on the
+// same registers, bounce 1 as k_bounce<false, false, 154> runs it (block-wide exact-test
+// exchange), and only then the compaction, into the buffer bounce 1 writes.  82 % of the camera
+// paths survive bounce 0: writing them out compacted and reading them straight back is the largest
+// single piece of path traffic of the frame, and with it go a geom-table staging, a block_append
+// and a launch.  Bounce 1 runs with the dead camera paths as idle lanes in the pre-test and the
+// shading; the exact tests are dealt out over the block, so idle lanes cost nothing there.
+// Per-path arithmetic, RNG keys and the gather are those of k_bounce, so the image is the same
+// bit for bit; the survivors of bounce 0 are counted into cnt[1] as k_tail counts (one atomic per
+// block), those of bounce 1 are appended to cnt[2] of the block's segment.  The exchange's region
+// follows the geom table as in k_bounce; the camera queue needs none of its own, so the block's
+// LDS is that of k_bounce<false, false, 154>.
+template <int VAR>
+__global__ __launch_bounds__(BLOCK) void k_head(SceneDev sc, PathBuf out, FrameCtl* ctl, float* __restrict__ image,
+                                               int seg_stride) {
+    extern __shared__ float4 s_dyn[];
+    const int iter = ctl->iter;
+    const bool to_plane = ctl->batch > 1 || ctl->plane != 0;   // gather into the frame planes
+    const int n = ctl->cnt[0][0][0];                           // local_pixels x batch
+    const int block_start = blockIdx.x * BLOCK;
+    if (block_start >= n) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    DevGeomHot* s_geoms = reinterpret_cast<DevGeomHot*>(s_dyn);
+    BlockLds* s_block = reinterpret_cast<BlockLds*>(s_dyn + lds_geom_f4(sc));
+    // the per-wave survivor counts of bounce 0 borrow the exchange's result rows: block_intersect
+    // first writes them after its own first barrier, which no wave passes before it has read these
+    int* s_cnt = reinterpret_cast<int*>(s_block->rt);
+    const int gid = block_start + tid;
+    const bool active = gid < n;
+    PathReg p;
+    p.rb = 0;
+    if (active) {
+        const int slot = gid / sc.shard.local_pixels;
+        p = camera_ray(sc.cam, iter + slot, sc.trace_depth, shard_pixel(sc, gid - slot * sc.shard.local_pixels));
+        p.slot = slot;
+    }
+    stage_geoms(sc, s_dyn);
+    const int seg = blockIdx.x & (NSEG - 1);
+    // bounce 0
+    if (active && p.rb > 0) {
+        const Hit h = intersect_scene_q<false, false, true, true>(sc, s_geoms, p.o, p.d, nullptr);
+        shade_path<(VAR & VAR_NO_TEX) == 0>(sc, p, h, iter + p.slot, [&]() { return hit_attr(sc, h); });
+    }
+    bool live = active && p.rb > 0;
+    if (active && !live) gather_into_image(image, sc, to_plane, p);
+    {   // paths entering bounce 1 (k_bounce's survivor count for the camera bounce)
+        const uint64_t m = __ballot(live);
+        if (lane == 0) s_cnt[tid >> 6] = __popcll(m);
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int i = 0; i < BLOCK / 64; ++i) tot += s_cnt[i];
+        if (tid == 0 && tot) atomicAdd(&ctl->cnt[1][seg][0], tot);
+        if (tot == 0) return;         // block-uniform
+    }
+    // bounce 1
+    float qt = 0.f;
+    int qw = -1;
+    f3 qs = mk(0.f, 0.f, 0.f);
+    block_intersect<false>(sc, s_geoms, live, p.o, p.d, s_block, qt, qw, qs);
+    if (live) {
+        const Hit h = finish_hit<false>(sc, p.o, p.d, nullptr, qt, qw, qs);
+        shade_path<(VAR & VAR_NO_TEX) == 0>(sc, p, h, iter + p.slot, [&]() { return hit_attr(sc, h); });
+        if (p.rb <= 0) gather_into_image(image, sc, to_plane, p);
+    }
+    const bool surv = live && p.rb > 0;
+    int si, unused;
+    block_append<false>(surv, &ctl->cnt[2][seg][0], false, nullptr, si, unused);
+    if (surv) store_path(out, seg * seg_stride + si, p);
+}
+
 // VAR_BVH_SPLIT, second half of a bounce: the queued paths, 64 to a wave, traverse the mesh
 // (bvh_intersect_pairs via finish_hit, entering with their primitive winner), are shaded, and
 // gathered / compacted into the same output segments as k_bounce (blockIdx % NSEG; the host
@@ -1150,6 +1222,7 @@ struct Tuning {
     bool tail_off = false;                          // PT_TAIL=0: no k_tail launch
     bool tail_any_batch = false;                    // PT_TAIL_BATCH=1: k_tail for multi-frame passes too
     int tail_from = 0;                              // PT_TAIL_FROM: k_tail's first bounce (0: depth / 2)
+    bool head_fuse = true;                          // PT_HEAD_FUSE=0: bounces 0 and 1 as two k_bounce launches
     int64_t auto_paths = 0;                         // PT_AUTO_PATHS: auto pass size in paths (0: AUTO_BATCH_PATHS)
     bool f1_graph = false;                          // PT_F1_GRAPH=1: single-frame passes through a graph
     bool multi_f1_direct = false;                   // PT_MULTI_F1_DIRECT=1: shards' single frames launched directly
@@ -1190,6 +1263,7 @@ Tuning read_tuning() {
     t.tail_off = num("PT_TAIL", 1) == 0;
     t.tail_any_batch = num("PT_TAIL_BATCH", 0) != 0;
     t.tail_from = (int)num("PT_TAIL_FROM", 0);
+    t.head_fuse = num("PT_HEAD_FUSE", 1) != 0;
     t.auto_paths = num("PT_AUTO_PATHS", 0);
     t.f1_graph = num("PT_F1_GRAPH", 0) != 0;
     t.multi_f1_direct = num("PT_MULTI_F1_DIRECT", 0) != 0;
@@ -1538,6 +1612,17 @@ void launch_compact(PathBuf pi, PathBuf po, const int* n_in, int* n_out, int npa
 // traced together as one wavefront of local_pixels x batch paths.
 // single-frame passes of primitive-only scenes run bounces tail_from() .. depth-1 as one k_tail
 // launch (PT_TAIL=0 turns it off for A/B); 0: no tail launch
+// Bounces 0 and 1 as one k_head launch (PT_HEAD_FUSE=0 turns it off for A/B): primitive-only
+// scenes whose geom table fits in LDS, on the default kernel variants only (no section counters,
+// no material grouping), passes of any number of frames.
+bool head_fused() {
+    constexpr int V0 = VAR_CAND_QUEUE | VAR_BVH_FAST;
+    constexpr int V1 = VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BLOCK_REDIST;
+    const int var = gp->opts.variant & ~VAR_BVH_NODES;
+    return gp->tune.head_fuse && gp->opts.pipeline == PT_PIPELINE_FUSED && !gp->has_bvh &&
+           gp->sc.num_geoms <= LDS_GEOMS && gp->sc.trace_depth >= 2 &&
+           (effective_variant(true, var) & ~VAR_NO_TEX) == V0 && (effective_variant(false, var) & ~VAR_NO_TEX) == V1;
+}
 int tail_from(int batch) {
     const int depth = gp->sc.trace_depth;
     const bool lds = gp->sc.num_geoms <= LDS_GEOMS;
@@ -1546,7 +1631,8 @@ int tail_from(int batch) {
             (VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BLOCK_REDIST))
         return 0;
     const int from = gp->tune.tail_from;
-    return std::min(depth - 1, std::max(1, from > 0 ? from : depth / 2));
+    // k_head traces bounce 1 itself: the tail then starts at bounce 2 at the earliest
+    return std::min(depth - 1, std::max(head_fused() ? 2 : 1, from > 0 ? from : depth / 2));
 }
 
 int enqueue_pass_body(int batch) {
@@ -1556,7 +1642,18 @@ int enqueue_pass_body(int batch) {
     const int nbounces = std::max(1, depth);
     if (gp->opts.pipeline == PT_PIPELINE_FUSED) {
         const int t = tail_from(batch);
-        for (int b = 0; b < (t ? t : nbounces); ++b) {
+        const bool head = head_fused();
+        if (head) {   // bounces 0 and 1; profiled as bounce 0 (bounce 1's entry stays 0)
+            const size_t lds = geom_table_lds() + sizeof(BlockLds) + gp->tune.bounce_lds_pad;
+            if (gp->no_tex)
+                launch(100, k_head<VAR_NO_TEX>, dim3(nb), dim3(BLOCK), lds, gp->sc, pathbuf(0), gp->d_ctl, gp->d_image,
+                       gp->seg_stride);
+            else
+                launch(100, k_head<0>, dim3(nb), dim3(BLOCK), lds, gp->sc, pathbuf(0), gp->d_ctl, gp->d_image,
+                       gp->seg_stride);
+            HIPCHK(hipGetLastError());
+        }
+        for (int b = head ? 2 : 0; b < (t ? t : nbounces); ++b) {
             PathBuf in = pathbuf(b & 1), out = pathbuf((b + 1) & 1);
             launch_bounce(b == 0, gp->has_bvh, gp->opts.variant & ~VAR_BVH_NODES, dim3(nb), in, out, b);
             HIPCHK(hipGetLastError());
