@@ -19,6 +19,7 @@
 
 #include "pt/pt_libm.h"
 #include "pt/scene_structs.h"
+#include "pt_records.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));   // native vector: one dwordx4 load
 
@@ -118,49 +119,8 @@ PT_DEV f3 xform(const float* m, f3 v, float w) {
     return f3{r0, r1, r2};
 }
 
-// 192-byte geom: inverseTransform | transform | invTranspose (affine rows), a conservative
-// world-space box (center, half extents incl. a safety margin) used only to SKIP exact tests
-// that cannot change the result, + type + material
-// The first 112 bytes are what the exact tests read (DevGeomHot): the fused kernel stages only
-// that prefix in LDS, so a 44-geom table takes 4.9 KB instead of 8.4 KB of the block's LDS.
-struct DevGeomHot {
-    float inv[12];
-    float fwd[12];
-    int32_t type;
-    int32_t materialid;
-    int32_t away_axis;  // cubes: object axis of the smallest scale for the pre-test's "away" drop
-                        // (see away_on_axis); -1: none (spheres, or matrices too large to bound)
-    int32_t _pad0;
-};
-static_assert(sizeof(DevGeomHot) == 112, "DevGeomHot");
-struct DevGeom {
-    float inv[12];
-    float fwd[12];
-    int32_t type;
-    int32_t materialid;
-    int32_t away_axis;
-    int32_t _pad0;
-    float itr[12];
-    float box_lo[3];    // conservative world box (outward-rounded, margin included)
-    float box_hi[3];
-    int32_t _pad[2];
-};
-static_assert(sizeof(DevGeom) == 192, "DevGeom");
-static_assert(offsetof(DevGeom, itr) == sizeof(DevGeomHot), "DevGeomHot is DevGeom's prefix");
+// the prefix of a DevGeom the exact tests read (pt_records.h)
 PT_DEV const DevGeomHot& hot(const DevGeom& g) { return *reinterpret_cast<const DevGeomHot*>(&g); }
-
-
-// Per-geom record of the candidate pre-test (block_intersect / wave_intersect), 48 bytes read
-// as 3 float4 with no branch between them: the conservative world box of cull_geom, and the
-// inverse-matrix row of away_on_axis's axis (all zero, never "away", for spheres and for cubes
-// without one).
-struct DevCull {
-    float lo[3], hi[3];
-    float row[4];          // inv[a], inv[3 + a], inv[6 + a], inv[9 + a]
-    int32_t has_row;       // 1: a cube with an away axis (row valid)
-    float _pad;
-};
-static_assert(sizeof(DevCull) == 48, "DevCull");
 
 // The "away" case of geom_test's cube (see the comment there), on ONE object axis a, with
 // geom_test's own arithmetic for qo[a] and u[a] (xform row a).  True only when geom_test's slab
@@ -174,58 +134,6 @@ PT_DEV bool away_on_axis(const DevGeomHot& g, int a, f3 ro, f3 rd) {
     const float u = (m[a] * rd.x + m[3 + a] * rd.y) + m[6 + a] * rd.z;
     return (qo > 0.5f && u > 0.0f) || (qo < -0.5f && u < 0.0f);
 }
-
-// 64-byte material: only what shading reads (sceneStructs.h:36-57)
-struct DevMaterial {
-    float color[3];
-    float emittance;
-    float hasReflective, hasRefractive, roughness, metallic;
-    float ior;
-    int32_t hasTexture;
-    int32_t textureID;
-    int32_t hasBumpMap;
-    int32_t bumpID;
-    float bumpScale;
-    int32_t _pad[2];
-};
-static_assert(sizeof(DevMaterial) == 64, "DevMaterial");
-
-// 32-byte BVH node: (min.xyz, a) (max.xyz, b); internal: a = left, b = right (<0: none);
-// leaf (reference: triCount > 0 && start >= 0): a = start, b = -(triCount + 2)
-struct DevNode {
-    float4 lo;
-    float4 hi;
-};
-
-// The two children of one internal BVH node, 64 bytes (VAR_BVH_FAST layout): popping a node
-// costs ONE dependent record fetch that holds both child boxes and everything needed to push
-// them.  ref >= 0 names the child's own pair record when ref < num_pairs, else the leaf
-// ref - num_pairs, whose triangles sit in the 4-slot group hot4[4 * leaf ..]; leaves are numbered
-// in the reference's visit order (push left, push right, pop: right subtree first), so a smaller
-// hot4 index is an earlier triangle in the reference's DFS.  The cull constants are those of
-// cull_threshold for s = max triangle edge below the child (x 1.01), precomputed per child.
-struct DevPair {
-    float4 l_lo;   // left box min.xyz  | left ref (int bits)
-    float4 l_hi;   // left box max.xyz  | left cull constants (A | d, 16 bits each, pack_cull)
-    float4 r_lo;   // right box min.xyz | right ref (int bits)
-    float4 r_hi;   // right box max.xyz | right cull constants
-};
-
-// hot triangle record in leaf order (index k = node.start + i): 3 positions, 48 bytes
-struct DevTriHot {
-    float4 a;   // v0.xyz, v1.x
-    float4 b;   // v1.yz, v2.xy
-    float4 c;   // v2.z, triIndex (int bits), -, -
-};
-
-// cold triangle data, by reference triangle index (read once for the winner)
-struct DevTriCold {
-    float n0[3], n1[3], n2[3];   // vertex normals
-    float uv0[2], uv1[2], uv2[2];
-    float dpdu[3], dpdv[3];
-    int32_t materialID;
-    int32_t _pad;
-};
 
 // ------------------------------------------------------------------------------------------
 // RNG: utilhash (intersections.h:13-22) + thrust::minstd_rand + uniform_real_distribution<float>

@@ -14,30 +14,10 @@
 namespace ptd {
 
 constexpr int NSEG = 8;        // output segments of the fused compaction (one per XCD group)
-constexpr int LDS_GEOMS = 64;  // fused kernel: geom tables up to this size are staged in LDS
 constexpr int MAXB = 64;       // max trace depth supported by the frame control block
-constexpr int BLOCK = 256;     // threads per block of the per-path kernels
-constexpr int MAXSTACK = 64;   // reference BVH stack (intersections.cu:167)
 constexpr int CNT_PAD = 32;    // one 128-byte cache line per live counter (atomics on separate lines)
 
-// kernel variants (pt_options.variant bits), selectable at run time for in-process A/B
-enum : int {
-    VAR_WAVE_ATOMIC = 1,   // compaction: one atomic per wave, no block barrier
-    VAR_CAND_QUEUE = 2,    // intersection: per-lane queue of candidate geoms (see intersect_scene_q)
-    VAR_SECTION_TIMING = 4,    // tools only: per-wave shader-clock section times into g_sections
-    VAR_WAVE_REDIST = 8,   // intersection: the wave's (ray, candidate) pairs spread over all 64 lanes
-    VAR_BVH_FAST = 16,     // BVH: exact-decision fast AABB test, near-first order, certified t-culling
-    VAR_CTILE8 = 16,       // staged compaction: 8 items per thread (2048-item tiles)
-    VAR_BVH_SPLIT = 32,    // fused + BVH_FAST + pair layout: rays that enter the mesh's root box are
-                           // queued and traversed (then shaded) by k_bvh_bounce in full waves
-    VAR_BVH_NODES = 64,    // host only: BVH_FAST on the node array instead of the DevPair layout (A/B)
-    VAR_BLOCK_REDIST = 128,  // with VAR_WAVE_REDIST: the exchange spans the block (block_intersect)
-    VAR_MAT_GROUP = 512,   // fused MATERIAL_SORTING: the block's paths regrouped by material between
-                           // intersection and shading (group_by_material); set by pt_options.material_sort
-    VAR_NO_TEX = 1024,     // host-set: no material samples a texture or bump map, so the fused kernels'
-                           // shading is compiled without the texel fetches (whose registers otherwise set
-                           // the kernels' VGPR count and occupancy)
-};
+// (LDS_GEOMS, BLOCK, MAXSTACK and the kernel variant bits VAR_*: pt_records.h)
 
 struct CamDev {
     int resx, resy;
@@ -93,23 +73,7 @@ struct SceneDev {
     float grid_lo[3], grid_inv[3]; // cell = floor((o - grid_lo) * grid_inv), GRID_G per axis
 };
 
-// The candidate table's resolution: GRID_G^3 origin cells x 6 faces x GRID_B^2 direction bins.
-// An entry is the AND of one mask per ratio bin (build_candidate_table), so the table is stored
-// separably (PT_GRID_SEP): 2 GRID_B masks per (cell, face), 2.65 MB at 12 / 16 (L2-resident).
-// 16 / 16 against 8 / 8: khaslana superset 5.68 -> 3.60 per ray, 13.8 -> 8.4 at the wave maximum,
-// frame -3 %; 12 / 16 times the same as 16 / 16 with 10 % less k_bounce traffic
-#ifndef PT_GRID_G
-#define PT_GRID_G 12
-#endif
-#ifndef PT_GRID_B
-#define PT_GRID_B 16
-#endif
-#ifndef PT_GRID_SEP
-#define PT_GRID_SEP 1
-#endif
-constexpr int GRID_G = PT_GRID_G;
-constexpr int GRID_B = PT_GRID_B;
-constexpr int GRID_MIN_GEOMS = 16;
+// (the candidate table's resolution GRID_G / GRID_B / PT_GRID_SEP: pt_records.h)
 
 // frame control block (device memory); zeroed / advanced by k_frame_begin every frame
 struct FrameCtl {
@@ -912,7 +876,7 @@ PT_DEV float cull_entry(const DevGeom& g, const CullRay& c) {   // +inf: certain
     return (t1 >= t0) ? t0 : __builtin_inff();
 }
 // The pre-test from the candidate table (sc.grid): the table gives each lane a superset of the
-// geoms its ray can hit at all -- built on the host (pt_init, build_candidate_table) by interval
+// geoms its ray can hit at all -- built on the host (host/scene_layout.cpp, build_candidate_table) by interval
 // arithmetic over every origin in the cell (grown by the cell computation's rounding) and every
 // direction in the bin (grown by the bin computation's rounding), against the same conservative
 // world boxes the pre-test uses, which contain every exact hit point.  Each lane then runs the
@@ -1112,7 +1076,8 @@ PT_DEV bool certain_exact_miss(const DevGeomHot& g, f3 ro, f3 rd, bool bounded) 
 // cull_geom), as a candidate mask (bit i = geom i), minus the one cube the ray certainly leaves
 // (certain_exact_miss).  Records are read four geoms (12 float4, 192 B) at a time through the
 // scalar cache, all loads of a group issued before any arithmetic; the host pads the record array
-// to a multiple of 4, and bits of pad records are masked off by the (wave-uniform) index test.
+// to a multiple of 4 (CULL_GROUP, pt_records.h), and bits of pad records are masked off by the
+// (wave-uniform) index test.
 // The "away" drop is evaluated for ONE cube per lane: the last kept cube with an away axis whose
 // box holds the ray's origin (t0 <= 0: every slab entry behind the origin) -- the surface a
 // bounce ray leaves.  A ray outside a cube's box that points away from it on an axis already
@@ -1120,9 +1085,6 @@ PT_DEV bool certain_exact_miss(const DevGeomHot& g, f3 ro, f3 rd, bool bounded) 
 // inside; a cube it is not applied to stays a candidate and its exact test rejects it (same
 // results).  Evaluating the row for every kept cube instead cost each wave ~14 instructions per
 // cube, since some lane of the wave keeps nearly every wall.
-#ifndef CULL_GROUP
-#define CULL_GROUP 4
-#endif
 #ifndef XSCAN_BALLOT
 #define XSCAN_BALLOT 1
 #endif

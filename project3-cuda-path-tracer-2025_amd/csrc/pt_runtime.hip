@@ -41,7 +41,7 @@
 #include "pt_kernels.h"
 #include "pt_denoise_kernels.h"
 #include "pt_naive_mesh_kernels.h"
-#include "trav_tree.h"
+#include "scene_layout.h"
 
 using namespace ptd;
 
@@ -1044,7 +1044,7 @@ __global__ __launch_bounds__(BLOCK) void k_compact_scatter(const float4* __restr
 }
 
 // ---- stable counting sort of materialId (MATERIAL_SORTING, pathtrace.cu:730-735) ----
-constexpr int MAXMAT = 256;
+// (at most MAXMAT keys, pt_records.h)
 
 // per-tile key histogram, tile = STILE items
 __global__ __launch_bounds__(BLOCK) void k_sort_hist(const int* __restrict__ keys, const int* n_ptr, int nkeys,
@@ -1333,7 +1333,7 @@ struct State {
     float* d_image = nullptr;
     FrameCtl* d_ctl = nullptr;
     float* d_contrib = nullptr;      // passes of F > 1 frames: F planes of pixels_total float3
-    unsigned long long* d_grid = nullptr;   // the pre-test's candidate table (build_candidate_table)
+    unsigned long long* d_grid = nullptr;   // the pre-test's candidate table (scene_layout.cpp, build_candidate_table)
     int batch = 1;                   // frames per pass (pt_options.frames_per_pass, resolved)
     bool split = false;              // VAR_BVH_SPLIT active (fused, fast BVH on the pair layout)
     bool no_tex = false;             // no textured / bump-mapped material (VAR_NO_TEX kernels)
@@ -2116,176 +2116,6 @@ int pass_frames(int remaining) {
     return (remaining + passes - 1) / passes;
 }
 
-// max DFS stack the reference traversal can reach on this tree (no culling)
-int bvh_max_stack(const pt_bvh_node* nodes, int n) {
-    if (n <= 0) return 0;
-    std::vector<int> st;
-    st.push_back(0);
-    size_t mx = 1;
-    std::vector<char> seen(n, 0);
-    while (!st.empty()) {
-        int i = st.back();
-        st.pop_back();
-        if (i < 0 || i >= n || seen[i]) continue;
-        seen[i] = 1;
-        const pt_bvh_node& nd = nodes[i];
-        if (nd.triCount > 0 && nd.start >= 0) continue;
-        if (nd.left >= 0) st.push_back(nd.left);
-        if (nd.right >= 0) st.push_back(nd.right);
-        mx = std::max(mx, st.size());
-    }
-    return (int)mx;
-}
-
-// levels of the tree below node 0 (root = 1); -1 for a malformed tree (a child out of range or
-// reached twice).  The near-first traversals (VAR_BVH_FAST) push at most one entry per level.
-int bvh_height(const pt_bvh_node* nodes, int n) {
-    if (n <= 0) return 0;
-    std::vector<std::pair<int, int>> st{{0, 1}};
-    std::vector<char> seen(n, 0);
-    int h = 0;
-    while (!st.empty()) {
-        const int i = st.back().first, d = st.back().second;
-        st.pop_back();
-        if (i < 0 || i >= n || seen[i]) return -1;
-        seen[i] = 1;
-        h = std::max(h, d);
-        const pt_bvh_node& nd = nodes[i];
-        if (nd.triCount > 0 && nd.start >= 0) continue;
-        if (nd.left >= 0) st.push_back({nd.left, d + 1});
-        if (nd.right >= 0) st.push_back({nd.right, d + 1});
-    }
-    return h;
-}
-
-// The pre-test's candidate table (SceneDev::grid, read by grid_superset): GRID_G^3 origin cells
-// over the scene x 6 dominant-axis faces x GRID_B^2 bins of the two other direction ratios
-// (d_i / |d_k| in [-1, 1]).  Entry bit g is set when SOME ray with its origin in the cell and its
-// direction in the bin can reach geom g's conservative world box at a nonnegative distance --
-// interval arithmetic in double along the dominant axis (the distance interval tau) and then on
-// the other two axes (origin interval + ratio interval x tau interval), a superset of the real
-// condition.  Every exact hit point lies in that box (the pre-test's premise, cull_geom), so a geom
-// outside the entry cannot be hit.  The cells are grown by far more than the device's float
-// cell computation can be off, the bins likewise for its rcp-based ratio, the boxes by 1e-6 of
-// the scene.  The two ratio axes are bounded independently, so an entry is the AND of one mask
-// per bin of each: with PT_GRID_SEP the table holds those 2 GRID_B masks per (cell, face) and the
-// device ANDs them (the same entries in 2 / GRID_B of the words).  Returns false (no table) for
-// scenes whose geom boxes are not finite.
-bool build_candidate_table(const std::vector<DevCull>& culls, int ng, const pt_vec3& cam,
-                           std::vector<unsigned long long>& table, float lo_out[3], float inv_out[3]) {
-    double lo[3] = {cam.x, cam.y, cam.z}, hi[3] = {cam.x, cam.y, cam.z};
-    for (int g = 0; g < ng; ++g)
-        for (int a = 0; a < 3; ++a) {
-            if (!(std::fabs(culls[g].lo[a]) < 1e17f && std::fabs(culls[g].hi[a]) < 1e17f)) return false;
-            lo[a] = std::min(lo[a], (double)culls[g].lo[a]);
-            hi[a] = std::max(hi[a], (double)culls[g].hi[a]);
-        }
-    double ext = 1.0;
-    for (int a = 0; a < 3; ++a) ext = std::max({ext, std::fabs(lo[a]), std::fabs(hi[a])});
-    double cs[3];
-    for (int a = 0; a < 3; ++a) {
-        lo[a] -= 1e-3 * ext;
-        hi[a] += 1e-3 * ext;
-        lo_out[a] = (float)lo[a];
-        lo[a] = lo_out[a];                                  // the device's origin of the cells
-        inv_out[a] = (float)(GRID_G / (hi[a] - lo[a]));
-        cs[a] = 1.0 / (double)inv_out[a];                   // the device's cell size
-    }
-    const double cm = 1e-6 * ext, bin_eps = 1e-5;
-    const int G = GRID_G, B = GRID_B;
-    table.assign((size_t)G * G * G * 6 * (PT_GRID_SEP ? 2 * B : B * B), 0ull);
-    std::vector<double> ta(ng), tb(ng);
-    std::vector<unsigned long long> mi(B), mj(B);
-    for (int cz = 0; cz < G; ++cz)
-        for (int cy = 0; cy < G; ++cy)
-            for (int cx = 0; cx < G; ++cx) {
-                const int c[3] = {cx, cy, cz};
-                double cl[3], ch[3];
-                for (int a = 0; a < 3; ++a) {
-                    cl[a] = lo[a] + c[a] * cs[a] - (1e-4 * cs[a] + cm);
-                    ch[a] = lo[a] + (c[a] + 1) * cs[a] + (1e-4 * cs[a] + cm);
-                }
-                const int cell = (cz * G + cy) * G + cx;
-                for (int face = 0; face < 6; ++face) {
-                    const int k = face / 2, i = (k + 1) % 3, j = (k + 2) % 3;
-                    const double s = (face & 1) ? 1.0 : -1.0;
-                    unsigned long long mk_ = 0;
-                    for (int g = 0; g < ng; ++g) {   // distance along axis k to reach the box's k-slab
-                        const double bl = culls[g].lo[k] - cm, bh = culls[g].hi[k] + cm;
-                        double a0 = s > 0 ? bl - ch[k] : cl[k] - bh, a1 = s > 0 ? bh - cl[k] : ch[k] - bl;
-                        a0 = std::max(a0, -cm);
-                        ta[g] = a0;
-                        tb[g] = a1;
-                        if (a1 >= a0) mk_ |= 1ull << g;
-                    }
-                    for (int axis = 0; axis < 2; ++axis) {
-                        const int a = axis == 0 ? i : j;
-                        std::vector<unsigned long long>& m = axis == 0 ? mi : mj;
-                        for (int b = 0; b < B; ++b) {
-                            const double r0 = (b == 0 ? -1.0 : -1.0 + 2.0 * b / B) - bin_eps;
-                            const double r1 = (b == B - 1 ? 1.0 : -1.0 + 2.0 * (b + 1) / B) + bin_eps;
-                            unsigned long long bits = 0;
-                            for (int g = 0; g < ng; ++g) {
-                                if (!((mk_ >> g) & 1)) continue;
-                                const double p[4] = {r0 * ta[g], r0 * tb[g], r1 * ta[g], r1 * tb[g]};
-                                const double pl = std::min({p[0], p[1], p[2], p[3]});
-                                const double ph = std::max({p[0], p[1], p[2], p[3]});
-                                if (cl[a] + pl <= (double)culls[g].hi[a] + cm && ch[a] + ph >= (double)culls[g].lo[a] - cm)
-                                    bits |= 1ull << g;
-                            }
-                            m[b] = bits;
-                        }
-                    }
-                    if (PT_GRID_SEP) {   // the device ANDs the two bins' masks
-                        unsigned long long* row = &table[((size_t)cell * 6 + face) * 2 * B];
-                        for (int b = 0; b < B; ++b) {
-                            row[b] = mi[b];
-                            row[B + b] = mj[b];
-                        }
-                        continue;
-                    }
-                    unsigned long long* row = &table[((size_t)cell * 6 + face) * B * B];
-                    for (int bu = 0; bu < B; ++bu)
-                        for (int bv = 0; bv < B; ++bv) row[bu * B + bv] = mi[bu] & mj[bv];
-                }
-            }
-    return true;
-}
-
-// Every inner node's box contains both children's boxes and every leaf's box contains its
-// triangles' vertices, with ordered (non-NaN) bounds -- true of every tree scene.cpp:428-441
-// builds (each box is the min / max over its own triangles).  The reference then visits a leaf
-// iff the leaf's own box passes, which is what a different hierarchy above the
-// leaves and the certified t-culls need.  Called after the structural checks (children and
-// triIndices in range).
-bool bvh_boxes_nested(const pt_scene_view& s) {
-    auto inside = [](const pt_vec3& lo, const pt_vec3& hi, const pt_vec3& a, const pt_vec3& b) {
-        return lo.x <= a.x && lo.y <= a.y && lo.z <= a.z && b.x <= hi.x && b.y <= hi.y && b.z <= hi.z;
-    };
-    for (int i = 0; i < s.num_bvh_nodes; ++i) {
-        const pt_bvh_node& nd = s.bvh_nodes[i];
-        if (nd.triCount > 0 && nd.start >= 0) {
-            for (int k = 0; k < nd.triCount; ++k) {
-                const int64_t j = (int64_t)nd.start + k;
-                if (j >= s.num_tri_indices) return false;
-                const int ti = s.tri_indices[j];
-                if (ti < 0 || ti >= s.num_triangles) return false;
-                const pt_triangle& t = s.triangles[ti];
-                for (const pt_vertex* v : {&t.v1, &t.v2, &t.v3})
-                    if (!inside(nd.aabb.min, nd.aabb.max, v->position, v->position)) return false;
-            }
-            continue;
-        }
-        for (int c : {nd.left, nd.right}) {
-            if (c < 0) continue;
-            if (c >= s.num_bvh_nodes) return false;
-            const pt_bvh_node& ch = s.bvh_nodes[c];
-            if (!inside(nd.aabb.min, nd.aabb.max, ch.aabb.min, ch.aabb.max)) return false;
-        }
-    }
-    return true;
-}
-
 template <class T>
 void dfree(T*& p) {
     if (p) (void)hipFree((void*)p);
@@ -2913,7 +2743,7 @@ void pt_default_options(pt_options* o) {
     o->shard_rows = 8;
     o->block_size = BLOCK;
     // fastest in the in-process A/B (tools/ab_variants.py); every variant is bit-identical
-    o->variant = VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BVH_SPLIT | VAR_BLOCK_REDIST;
+    o->variant = VAR_DEFAULT;
     o->frames_per_pass = 0;        // auto
     // several GPUs behind one pathtrace(): the drop-in and pt_render reach it through the environment
     o->num_devices = 0;
@@ -2972,32 +2802,6 @@ int auto_batch(int local_pixels) {
     return f;
 }
 
-// cold triangle data by reference triangle index (vertex normals, uvs, tangents, material)
-static int32_t fill_cold(const pt_scene_view* s, std::vector<DevTriCold>& cold) {
-    cold.resize(s->num_triangles);
-    for (int i = 0; i < s->num_triangles; ++i) {
-        const pt_triangle& t = s->triangles[i];
-        DevTriCold& c = cold[i];
-        memset(&c, 0, sizeof c);
-        const pt_vertex* v[3] = {&t.v1, &t.v2, &t.v3};
-        float* ns[3] = {c.n0, c.n1, c.n2};
-        float* uvs[3] = {c.uv0, c.uv1, c.uv2};
-        for (int k = 0; k < 3; ++k) {
-            ns[k][0] = v[k]->normal.x;
-            ns[k][1] = v[k]->normal.y;
-            ns[k][2] = v[k]->normal.z;
-            uvs[k][0] = v[k]->uv.x;
-            uvs[k][1] = v[k]->uv.y;
-        }
-        c.dpdu[0] = t.dpdu.x; c.dpdu[1] = t.dpdu.y; c.dpdu[2] = t.dpdu.z;
-        c.dpdv[0] = t.dpdv.x; c.dpdv[1] = t.dpdv.y; c.dpdv[2] = t.dpdv.z;
-        c.materialID = t.materialID;
-        if (t.materialID < 0 || t.materialID >= std::max(1, s->num_materials))
-            return fail(PT_E_INVALID, "triangle %d material %d out of range", i, t.materialID);
-    }
-    return PT_OK;
-}
-
 // one context (gp): the whole pathtraceInit for one device, or for shard k of a multi-device
 // context; `share` contexts live on this device (auto F divides its free memory among them)
 static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
@@ -3045,512 +2849,40 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     if (o.frames_per_pass < 0 || o.frames_per_pass > MAXF)
         return fail(PT_E_INVALID, "frames_per_pass must be 0 (auto) .. %d", MAXF);
 
-    // ---- scene -> device records ----
-    std::vector<DevGeom> geoms(s->num_geoms);
-    for (int i = 0; i < s->num_geoms; ++i) {
-        const pt_geom& gg = s->geoms[i];
-        DevGeom& d = geoms[i];
-        memset(&d, 0, sizeof d);
-        for (int c = 0; c < 4; ++c)
-            for (int r = 0; r < 3; ++r) {
-                d.inv[c * 3 + r] = gg.inverseTransform.m[c][r];
-                d.fwd[c * 3 + r] = gg.transform.m[c][r];
-                d.itr[c * 3 + r] = gg.invTranspose.m[c][r];
-            }
-        d.type = gg.type;
-        d.materialid = gg.materialid;
-        // away_on_axis pre-test: the object axis of smallest world scale (a wall's thin axis,
-        // the face a ray leaving it crosses); only when the inverse matrix is bounded so that
-        // dot(u, u) < inf is guaranteed for |rd| components <= 1e3
-        d.away_axis = -1;
-        if (gg.type == PT_CUBE) {
-            double big = 0.0;
-            for (int c = 0; c < 4; ++c)
-                for (int r = 0; r < 3; ++r) big = std::max(big, std::fabs((double)gg.inverseTransform.m[c][r]));
-            if (big <= 1e12) {
-                double best = 1e300;
-                for (int a = 0; a < 3; ++a) {
-                    const double len = std::sqrt((double)gg.transform.m[a][0] * gg.transform.m[a][0] +
-                                                 (double)gg.transform.m[a][1] * gg.transform.m[a][1] +
-                                                 (double)gg.transform.m[a][2] * gg.transform.m[a][2]);
-                    if (len < best) {
-                        best = len;
-                        d.away_axis = a;
-                    }
-                }
-            }
-        }
-    }
-    // conservative world boxes for cull_geom: the transformed unit cube (contains the radius-0.5
-    // sphere too), grown by a margin far above every rounding the exact test can make (1e-3 of
-    // the largest half extent + 1e-3 absolute; object-space pull-back is 1e-4 times the scale)
-    // and above the cull's own fma/rcp error for ray origins anywhere in the scene (1e-6 of the
-    // scene extent), then rounded outward.
+    // ---- scene -> the device buffers' byte images (host/scene_layout.cpp) ----
+    pth::LayoutParams lp;
+    lp.bvh = o.bvh != 0;
+    lp.variant = o.variant;
+    lp.naive = naive;
+    lp.bvh_tree_ref = gp->tune.bvh_tree_ref;
+    lp.bvh_tree_info = gp->tune.bvh_tree_info;
+    lp.bvh_bfs_levels = gp->tune.bvh_bfs_levels;
+    lp.bvh_quad = gp->tune.bvh_quad;
+    lp.grid = gp->tune.grid;
+    // the traversal kernels keep one stack entry per tree level in LDS (BLOCK x 4 B each): a tree of
+    // height h needs (h + 1) KB per block, so the SAH tree's height is bounded to what still lets
+    // BVH_WAVES blocks share a CU's 160 KB (21 levels; the 262k / 1.0M stand-ins' SAH trees are
+    // 24 / 26 high unbounded: 6 / 5 blocks)
+    lp.sah_max_height = gp->tune.bvh_max_height > 0 ? gp->tune.bvh_max_height
+                        : gp->tune.bvh_max_height == 0
+                            ? (1 << 30)
+                            : (int)(163840 / ((size_t)BVH_WAVES * BLOCK * sizeof(int))) - 1;
+    pth::SceneLayout L;
     {
-        double extent = std::max({std::fabs((double)s->camera.position.x), std::fabs((double)s->camera.position.y),
-                                  std::fabs((double)s->camera.position.z), 1.0});
-        std::vector<float> bc(3 * (size_t)s->num_geoms), bh(3 * (size_t)s->num_geoms);
-        std::vector<char> fin(s->num_geoms);
-        for (int i = 0; i < s->num_geoms; ++i) {
-            DevGeom& d = geoms[i];
-            float hmax = 0.f;
-            for (int r = 0; r < 3; ++r) {
-                bc[3 * i + r] = d.fwd[9 + r];
-                bh[3 * i + r] = 0.5f * (std::fabs(d.fwd[r]) + std::fabs(d.fwd[3 + r]) + std::fabs(d.fwd[6 + r]));
-                hmax = std::max(hmax, bh[3 * i + r]);
-            }
-            for (int r = 0; r < 3; ++r) bh[3 * i + r] += 1e-3f * hmax + 1e-3f * std::max(1.0f, hmax);
-            fin[i] = std::isfinite(hmax) && std::isfinite(bc[3 * i]) && std::isfinite(bc[3 * i + 1]) &&
-                     std::isfinite(bc[3 * i + 2]) && hmax < 1e17f;
-            if (fin[i])
-                for (int r = 0; r < 3; ++r)
-                    extent = std::max(extent, std::fabs((double)bc[3 * i + r]) + (double)bh[3 * i + r]);
-        }
-        for (int t = 0; t < s->num_triangles; ++t) {
-            const pt_vertex* v[3] = {&s->triangles[t].v1, &s->triangles[t].v2, &s->triangles[t].v3};
-            for (auto* x : v) {
-                double m = std::max({std::fabs((double)x->position.x), std::fabs((double)x->position.y),
-                                     std::fabs((double)x->position.z)});
-                if (std::isfinite(m)) extent = std::max(extent, m);
-            }
-        }
-        const float emargin = (float)std::min(1e-6 * extent, 1e17);
-        for (int i = 0; i < s->num_geoms; ++i) {
-            DevGeom& d = geoms[i];
-            for (int r = 0; r < 3; ++r) {
-                if (!fin[i]) {   // degenerate transform: a box that never culls
-                    d.box_lo[r] = -1e18f;
-                    d.box_hi[r] = 1e18f;
-                    continue;
-                }
-                const float h = bh[3 * i + r] + emargin;
-                d.box_lo[r] = std::nextafter(bc[3 * i + r] - h, -INFINITY);
-                d.box_hi[r] = std::nextafter(bc[3 * i + r] + h, INFINITY);
-            }
-        }
+        std::string err;
+        const int32_t rc = pth::build_scene_layout(*s, lp, L, err);
+        if (rc != PT_OK) return fail(rc, "%s", err.c_str());
     }
-    // padded to a multiple of CULL_GROUP records (cull_candidates reads that many at a time; pad
-    // bits are masked)
-    std::vector<DevCull> culls((std::max(1, s->num_geoms) + CULL_GROUP - 1) / CULL_GROUP * CULL_GROUP);
-    for (DevCull& c : culls) memset(&c, 0, sizeof c);
-    for (int i = 0; i < s->num_geoms; ++i) {
-        const DevGeom& d = geoms[i];
-        DevCull& c = culls[i];
-        memset(&c, 0, sizeof c);
-        for (int r = 0; r < 3; ++r) {
-            c.lo[r] = d.box_lo[r];
-            c.hi[r] = d.box_hi[r];
-        }
-        const int a = d.away_axis;
-        if (d.type == PT_CUBE && a >= 0 && a < 3) {
-            for (int k = 0; k < 4; ++k) c.row[k] = d.inv[3 * k + a];
-            c.has_row = 1;
-        }
-    }
-    std::vector<DevMaterial> mats(std::max(1, s->num_materials));
-    for (int i = 0; i < s->num_materials; ++i) {
-        const pt_material& m = s->materials[i];
-        DevMaterial& d = mats[i];
-        memset(&d, 0, sizeof d);
-        d.color[0] = m.color.x;
-        d.color[1] = m.color.y;
-        d.color[2] = m.color.z;
-        d.emittance = m.emittance;
-        d.hasReflective = m.hasReflective;
-        d.hasRefractive = m.hasRefractive;
-        d.roughness = m.roughness;
-        d.metallic = m.metallic;
-        d.ior = m.indexOfRefraction;
-        d.hasTexture = m.hasTexture ? 1 : 0;
-        d.textureID = m.textureID;
-        d.hasBumpMap = m.hasBumpMap ? 1 : 0;
-        d.bumpID = m.bumpID;
-        d.bumpScale = m.bumpScale;
-    }
-    // no material samples a texture or bump map: the fused kernels' texture-free build (VAR_NO_TEX)
-    gp->no_tex = true;
-    for (int i = 0; i < s->num_materials; ++i)
-        if (s->materials[i].hasTexture || s->materials[i].hasBumpMap) gp->no_tex = false;
-    // BVH: only when the reference would traverse it (BVH_ACCELERATION and a non-empty tree)
-    // (the naive mesh mode skips it whatever the options and the scene view say)
+    o.variant = L.variant;   // minus the near-first traversals, for a tree they cannot walk
+    gp->opts.variant = o.variant;
+    gp->no_tex = L.no_tex;
     gp->naive = naive;
-    gp->has_bvh = !naive && o.bvh && s->num_bvh_nodes > 0 && s->num_triangles > 0;
-    std::vector<DevNode> nodes;
-    std::vector<float4> node_aux;
-    std::vector<DevTriHot> hot;
-    std::vector<DevTriCold> cold;
-    std::vector<DevPair> pairs;      // VAR_BVH_FAST layout (empty: tree not representable)
-    std::vector<float4> quads;       // its 4-wide form (8 float4 per record; empty: not built)
-    int quad_stack = 0;              // stack entries the 4-wide traversal can need
-    std::vector<DevTriHot> hot4;
-    std::vector<float4> leaf9;
-    int pair_root_ref = 0, pair_count = 0, pair_ref_shift = 16;
-
-    float4 pair_root_lo{}, pair_root_hi{};
-    double cull_extent = 1.0;
-    if (gp->has_bvh) {
-        nodes.resize(s->num_bvh_nodes);
-        for (int i = 0; i < s->num_bvh_nodes; ++i) {
-            const pt_bvh_node& nd = s->bvh_nodes[i];
-            bool leaf = nd.triCount > 0 && nd.start >= 0;
-            int a = leaf ? nd.start : nd.left;
-            int b = leaf ? -(nd.triCount + 2) : (nd.right >= 0 ? nd.right : -1);
-            if (leaf && (int64_t)nd.start + nd.triCount > s->num_tri_indices)
-                return fail(PT_E_INVALID, "BVH leaf %d indexes past triIndices", i);
-            if (!leaf && (nd.left >= s->num_bvh_nodes || nd.right >= s->num_bvh_nodes))
-                return fail(PT_E_INVALID, "BVH node %d child out of range", i);
-            float fa, fb;
-            memcpy(&fa, &a, 4);
-            memcpy(&fb, &b, 4);
-            nodes[i].lo = make_float4(nd.aabb.min.x, nd.aabb.min.y, nd.aabb.min.z, fa);
-            nodes[i].hi = make_float4(nd.aabb.max.x, nd.aabb.max.y, nd.aabb.max.z, fb);
-        }
-        // per-node culling bounds and the reference's DFS visit rank (push left, push right, pop)
-        node_aux.assign(s->num_bvh_nodes, make_float4(0.f, 0.f, 0.f, 0.f));
-        {
-            double extent = std::max({1.0, std::fabs((double)s->camera.position.x),
-                                      std::fabs((double)s->camera.position.y), std::fabs((double)s->camera.position.z)});
-            for (int t = 0; t < s->num_triangles; ++t) {
-                const pt_vertex* v[3] = {&s->triangles[t].v1, &s->triangles[t].v2, &s->triangles[t].v3};
-                for (auto* x : v)
-                    extent = std::max({extent, std::fabs((double)x->position.x), std::fabs((double)x->position.y),
-                                       std::fabs((double)x->position.z)});
-            }
-            for (int i = 0; i < s->num_geoms; ++i)   // hit points on primitives are ray origins too
-                for (int r = 0; r < 3; ++r)
-                    extent = std::max(extent, std::fabs((double)geoms[i].box_lo[r]) + std::fabs((double)geoms[i].box_hi[r]));
-            cull_extent = extent;
-            std::vector<double> smax(s->num_bvh_nodes, -1.0);
-            // bottom-up max edge: children have larger indices than parents in the reference build,
-            // but compute it by explicit post-order to accept any valid tree
-            std::vector<int> order, st{0};
-            std::vector<char> seen(s->num_bvh_nodes, 0);
-            while (!st.empty()) {
-                int n = st.back();
-                st.pop_back();
-                if (n < 0 || n >= s->num_bvh_nodes || seen[n]) continue;
-                seen[n] = 1;
-                order.push_back(n);
-                const pt_bvh_node& nd = s->bvh_nodes[n];
-                if (!(nd.triCount > 0 && nd.start >= 0)) {
-                    if (nd.left >= 0) st.push_back(nd.left);
-                    if (nd.right >= 0) st.push_back(nd.right);
-                }
-            }
-            for (size_t k = order.size(); k-- > 0;) {
-                const int n = order[k];
-                const pt_bvh_node& nd = s->bvh_nodes[n];
-                double m = 0.0;
-                if (nd.triCount > 0 && nd.start >= 0) {
-                    for (int i = 0; i < nd.triCount; ++i) {
-                        const int ti = s->tri_indices[nd.start + i];
-                        if (ti < 0 || ti >= s->num_triangles) continue;   // rejected below
-                        const pt_triangle& t = s->triangles[ti];
-                        const double e1 = std::hypot((double)t.v2.position.x - t.v1.position.x,
-                                                     (double)t.v2.position.y - t.v1.position.y,
-                                                     (double)t.v2.position.z - t.v1.position.z);
-                        const double e2 = std::hypot((double)t.v3.position.x - t.v1.position.x,
-                                                     (double)t.v3.position.y - t.v1.position.y,
-                                                     (double)t.v3.position.z - t.v1.position.z);
-                        m = std::max({m, e1, e2});
-                    }
-                } else {
-                    if (nd.left >= 0) m = std::max(m, smax[nd.left]);
-                    if (nd.right >= 0) m = std::max(m, smax[nd.right]);
-                }
-                smax[n] = m;
-                const double sx = m * 1.01 + 1e-30;
-                const double c = 64.0 * std::ldexp(1.0, -24) * sx * sx / 1e-5;
-                node_aux[n].x = (float)std::min(c * 1.01, 1e30);
-                node_aux[n].y = (float)std::min(sx, 1e30);
-                node_aux[n].w = (float)std::min(c * extent * 1.01, 1e30);
-            }
-            // reference visit rank
-            int rank = 0;
-            st.assign(1, 0);
-            std::fill(seen.begin(), seen.end(), 0);
-            while (!st.empty()) {
-                int n = st.back();
-                st.pop_back();
-                if (n < 0 || n >= s->num_bvh_nodes) continue;
-                int r = rank++;
-                float fr;
-                memcpy(&fr, &r, 4);
-                node_aux[n].z = fr;
-                const pt_bvh_node& nd = s->bvh_nodes[n];
-                if (!(nd.triCount > 0 && nd.start >= 0) && !seen[n]) {
-                    seen[n] = 1;
-                    if (nd.left >= 0) st.push_back(nd.left);
-                    if (nd.right >= 0) st.push_back(nd.right);
-                }
-            }
-        }
-        hot.resize(s->num_tri_indices);
-        for (int k = 0; k < s->num_tri_indices; ++k) {
-            int ti = s->tri_indices[k];
-            if (ti < 0 || ti >= s->num_triangles) return fail(PT_E_INVALID, "triIndices[%d] out of range", k);
-            const pt_triangle& t = s->triangles[ti];
-            float fti;
-            memcpy(&fti, &ti, 4);
-            hot[k].a = make_float4(t.v1.position.x, t.v1.position.y, t.v1.position.z, t.v2.position.x);
-            hot[k].b = make_float4(t.v2.position.y, t.v2.position.z, t.v3.position.x, t.v3.position.y);
-            hot[k].c = make_float4(t.v3.position.z, fti, 0.f, 0.f);
-        }
-        RC(fill_cold(s, cold));
-        // traversal stack (LDS, MAXSTACK entries per lane at most).  The reference-order DFS needs
-        // bvh_max_stack entries -- more than 64 overflows the reference's own int stack[64]
-        // (intersections.cu:167), so such a tree is refused rather than traversed differently.
-        // The near-first traversals need up to height + 1; a tree too deep (or malformed) for
-        // that keeps the reference-order traversal.  No push is ever dropped.
-        const int ref_stack = bvh_max_stack(s->bvh_nodes, s->num_bvh_nodes);
-        if (ref_stack > MAXSTACK)
-            return fail(PT_E_UNSUPPORTED, "BVH needs a %d-entry traversal stack; the reference's holds %d "
-                        "(intersections.cu:167)", ref_stack, MAXSTACK);
-        const int tree_height = bvh_height(s->bvh_nodes, s->num_bvh_nodes);
-        // the near-first traversals (pair layout, SAH hierarchy, certified t-culls) rely on the
-        // boxes being nested as scene.cpp:428-441 builds them; a caller-supplied tree that is not
-        // keeps the reference-order traversal, which assumes nothing
-        if (tree_height < 0 || tree_height + 1 > MAXSTACK || !bvh_boxes_nested(*s)) {
-            o.variant &= ~(VAR_BVH_FAST | VAR_BVH_SPLIT);
-            gp->opts.variant = o.variant;
-        }
-        gp->stack_depth = std::max(2, ref_stack);
-        if (o.variant & VAR_BVH_FAST) gp->stack_depth = std::max(gp->stack_depth, tree_height + 1);
-        // VAR_BVH_FAST pair layout (DevPair): walk the tree in the reference's visit order
-        // (push left, push right, pop -> right subtree first), numbering internal nodes (pairs)
-        // and leaves (4-slot triangle groups).  Any tree this layout cannot hold exactly -- a
-        // missing child, a node reached twice, a leaf of more than 4 triangles, 2^24 refs or more
-        // (pack_ref's widest ref field) or a deeper tree than the stack -- keeps the node-array
-        // traversal.
-        {
-            const int nn = s->num_bvh_nodes;
-            std::vector<int> id(nn, -1);
-            std::vector<char> is_leaf(nn, 0);
-            std::vector<std::pair<int, int>> st{{0, 1}};
-            int P = 0, L = 0, height = 0;
-            bool ok = true;
-            std::vector<int> leaf_nodes;
-            while (!st.empty() && ok) {
-                const int n = st.back().first, d = st.back().second;
-                st.pop_back();
-                if (n < 0 || n >= nn || id[n] >= 0) { ok = false; break; }
-                height = std::max(height, d);
-                const pt_bvh_node& nd = s->bvh_nodes[n];
-                if (nd.triCount > 0 && nd.start >= 0) {
-                    if (nd.triCount > 4) ok = false;
-                    is_leaf[n] = 1;
-                    id[n] = L++;
-                    leaf_nodes.push_back(n);
-                } else {
-                    if (nd.left < 0 || nd.right < 0) { ok = false; break; }
-                    id[n] = P++;
-                    st.push_back({nd.left, d + 1});
-                    st.push_back({nd.right, d + 1});
-                }
-            }
-            if (ok) {   // internal refs breadth-first: the top levels share a few cache lines
-                std::vector<int> fifo{0};
-                int k = 0;
-                for (size_t h = 0; h < fifo.size(); ++h) {
-                    const int n = fifo[h];
-                    if (is_leaf[n]) continue;
-                    id[n] = k++;
-                    fifo.push_back(s->bvh_nodes[n].left);
-                    fifo.push_back(s->bvh_nodes[n].right);
-                }
-            }
-            ok = ok && (int64_t)P + L < (1 << 24) && height + 1 <= MAXSTACK && !(o.variant & VAR_BVH_NODES);
-            if (ok) {
-                auto ref = [&](int n) { return is_leaf[n] ? P + id[n] : id[n]; };
-                // cull_threshold_packed's constants for a child of cull size s (same c0 and E as
-                // SceneDev::cull_c0 / cull_E below), evaluated in double and rounded up
-                const float c0f = (float)(64.0 * std::ldexp(1.0, -24) / 1e-5 * 1.01 * (1.0 + 1e-5));
-                const float Ef = (float)(cull_extent * (1.0 + 1e-5));
-                auto pack_cull = [&](float sf) {
-                    auto up16 = [](double v) -> uint32_t {
-                        if (!(v >= 0.0)) v = HUGE_VAL;                  // NaN: never cull
-                        float f = (float)v;
-                        if ((double)f < v) f = std::nextafter(f, HUGE_VALF);
-                        uint32_t b;
-                        memcpy(&b, &f, 4);
-                        if (b & 0xffffu) b = (b & 0xffff0000u) + 0x10000u;   // up to 16 bits (inf stays inf)
-                        return b >> 16;
-                    };
-                    const double sd = sf, c = sd * sd * (double)c0f;
-                    const double A = c * sd * 1.002 + c * (double)Ef * (1.0 + 1e-6);
-                    const double d = 1.0 - (1.0 - 1e-6) / (1.0 + 2.0 * c + 2e-6);
-                    const uint32_t w = (up16(A) << 16) | up16(d);
-                    float f;
-                    memcpy(&f, &w, 4);
-                    return f;
-                };
-                // The hierarchy above the reference's leaves (trav_tree.h): a binned-SAH tree over
-                // them, its inner boxes the unions of their leaves' boxes, unless a leaf box has a
-                // NaN / infinite bound (the containment argument needs ordered bounds), the union
-                // differs from the reference root box, or the tree would not fit the stack.
-                // PT_BVH_TREE=ref (tools, A/B) keeps the reference's own hierarchy.
-                std::vector<pth::TravInner> tt;
-                int th = 0;
-                bool sah = !gp->tune.bvh_tree_ref && L >= 2;
-                if (sah) {
-                    std::vector<float> llo(3 * (size_t)L), lhi(3 * (size_t)L), ls(L);
-                    for (int k = 0; k < L; ++k) {
-                        const DevNode& nd = nodes[leaf_nodes[k]];
-                        llo[3 * k] = nd.lo.x; llo[3 * k + 1] = nd.lo.y; llo[3 * k + 2] = nd.lo.z;
-                        lhi[3 * k] = nd.hi.x; lhi[3 * k + 1] = nd.hi.y; lhi[3 * k + 2] = nd.hi.z;
-                        ls[k] = node_aux[leaf_nodes[k]].y;
-                    }
-                    // the traversal kernels keep one stack entry per tree level in LDS (BLOCK x 4 B each):
-                    // a tree of height h needs (h + 1) KB per block, so the height is bounded to what
-                    // still lets BVH_WAVES blocks share a CU's 160 KB (21 levels; the 262k / 1.0M
-                    // stand-ins' SAH trees are 24 / 26 high unbounded: 6 / 5 blocks)
-                    const int hmax = gp->tune.bvh_max_height > 0 ? gp->tune.bvh_max_height
-                                     : gp->tune.bvh_max_height == 0
-                                         ? (1 << 30)
-                                         : (int)(163840 / ((size_t)BVH_WAVES * BLOCK * sizeof(int))) - 1;
-                    sah = pth::build_sah_tree(llo, lhi, ls, tt, th, gp->tune.bvh_bfs_levels, hmax) && th + 1 <= MAXSTACK &&
-                          (int64_t)tt.size() + L < (1 << 24);
-                    if (sah) {   // the union of the leaves is the reference root box, bit for bit
-                        const pth::TravChild& a = tt[0].c[0];
-                        const pth::TravChild& b = tt[0].c[1];
-                        const float r[6] = {nodes[0].lo.x, nodes[0].lo.y, nodes[0].lo.z,
-                                            nodes[0].hi.x, nodes[0].hi.y, nodes[0].hi.z};
-                        for (int ax = 0; ax < 3; ++ax)
-                            sah = sah && std::min(a.lo[ax], b.lo[ax]) == r[ax] && std::max(a.hi[ax], b.hi[ax]) == r[3 + ax];
-                    }
-                }
-                if (sah) {
-                    P = (int)tt.size();
-                    pairs.resize(P);
-                    for (int i = 0; i < P; ++i) {
-                        DevPair& pr = pairs[i];
-                        float4* lo[2] = {&pr.l_lo, &pr.r_lo};
-                        float4* hi[2] = {&pr.l_hi, &pr.r_hi};
-                        for (int k = 0; k < 2; ++k) {
-                            const pth::TravChild& c = tt[i].c[k];
-                            const int rf = c.leaf ? P + c.ref : c.ref;
-                            float frf;
-                            memcpy(&frf, &rf, 4);
-                            *lo[k] = make_float4(c.lo[0], c.lo[1], c.lo[2], frf);
-                            *hi[k] = make_float4(c.hi[0], c.hi[1], c.hi[2], pack_cull(c.s));
-                        }
-                    }
-                    gp->stack_depth = std::max(gp->stack_depth, th + 1);
-                    gp->pair_depth = th + 1;
-                    // the 4-wide form of the same hierarchy: record q holds the children of binary
-                    // node n, an inner child replaced by its own two children (two levels per
-                    // record, one 128-B line); quad 0 is the root's.  Inner refs breadth-first over
-                    // the top levels, preorder below, as the pairs (PT_BVH_BFS_LEVELS / 2 levels).
-                    const bool quad_on = gp->tune.bvh_quad > 0;
-                    if (quad_on) {
-                        std::vector<pth::QuadRecord> qr;
-                        int qneed = 0;
-                        pth::build_quad_records(tt, std::max(0, gp->tune.bvh_bfs_levels / 2), qr, qneed);
-                        // the hand-over saves the stack depth in 7 bits (trav_saved_node): deeper
-                        // worst cases (trees far past the height bound) keep the pairs
-                        if (qneed + 1 > 96) qr.clear();
-                        const int Q = (int)qr.size();
-                        quads.assign(8 * (size_t)Q, make_float4(0.f, 0.f, 0.f, 0.f));
-                        for (int q = 0; q < Q; ++q) {
-                            float4* R = &quads[8 * (size_t)q];
-                            float* f[8] = {&R[0].x, &R[1].x, &R[2].x, &R[3].x, &R[4].x, &R[5].x, &R[6].x, &R[7].x};
-                            for (int i = 0; i < 4; ++i) {
-                                int rf = -1;   // no child
-                                if (i < qr[q].n) {
-                                    const pth::TravChild& c = qr[q].c[i];
-                                    for (int a = 0; a < 3; ++a) {
-                                        f[a][i] = c.lo[a];
-                                        f[3 + a][i] = c.hi[a];
-                                    }
-                                    rf = c.leaf ? Q + c.ref : c.ref;
-                                    f[7][i] = pack_cull(c.s);
-                                }
-                                memcpy(&f[6][i], &rf, 4);
-                            }
-                        }
-                        quad_stack = Q > 0 ? qneed + 1 : 0;
-                        gp->stack_depth = std::max(gp->stack_depth, quad_stack);
-                        gp->pair_depth = std::max(gp->pair_depth, quad_stack);   // the push bound covers both
-                        if (gp->tune.bvh_tree_info)
-                            fprintf(stderr, "pt_init: 4-wide records %d (pairs %d), stack %d entries\n", Q, P, quad_stack);
-                    }
-                    if (gp->tune.bvh_tree_info)
-                        fprintf(stderr, "pt_init: SAH traversal tree over %d reference leaves, height %d (reference %d)\n", L,
-                                th, height);
-                }
-                pairs.resize(std::max(1, P));
-                for (int n = 0; n < nn && !sah; ++n) {
-                    if (id[n] < 0 || is_leaf[n]) continue;
-                    const pt_bvh_node& nd = s->bvh_nodes[n];
-                    DevPair& pr = pairs[id[n]];
-                    const int kids[2] = {nd.left, nd.right};
-                    float4* lo[2] = {&pr.l_lo, &pr.r_lo};
-                    float4* hi[2] = {&pr.l_hi, &pr.r_hi};
-                    for (int k = 0; k < 2; ++k) {
-                        const int c = kids[k];
-                        const int rf = ref(c);
-                        float frf;
-                        memcpy(&frf, &rf, 4);
-                        *lo[k] = make_float4(nodes[c].lo.x, nodes[c].lo.y, nodes[c].lo.z, frf);
-                        *hi[k] = make_float4(nodes[c].hi.x, nodes[c].hi.y, nodes[c].hi.z, pack_cull(node_aux[c].y));
-                    }
-                }
-                hot4.assign(4 * (size_t)L, DevTriHot{});
-                for (int k = 0; k < L; ++k) {
-                    const pt_bvh_node& nd = s->bvh_nodes[leaf_nodes[k]];
-                    for (int i = 0; i < nd.triCount; ++i) hot4[4 * (size_t)k + i] = hot[nd.start + i];
-                    const int cnt = nd.triCount;
-                    memcpy(&hot4[4 * (size_t)k].c.z, &cnt, 4);
-                }
-                // trav_step's leaf records: component k of the 4 slots in one float4, positions
-                // as v0 and the float edges v1 - v0, v2 - v0 (tri_test's own first rounding)
-                leaf9.assign(9 * (size_t)L, make_float4(0.f, 0.f, 0.f, 0.f));
-                for (int k = 0; k < L; ++k)
-                    for (int i = 0; i < 4; ++i) {
-                        const DevTriHot& h = hot4[4 * (size_t)k + i];
-                        const float v0[3] = {h.a.x, h.a.y, h.a.z}, v1[3] = {h.a.w, h.b.x, h.b.y},
-                                    v2[3] = {h.b.z, h.b.w, h.c.x};
-                        float comp9[9];
-                        for (int a = 0; a < 3; ++a) {
-                            comp9[a] = v0[a];
-                            comp9[3 + a] = v1[a] - v0[a];
-                            comp9[6 + a] = v2[a] - v0[a];
-                        }
-                        for (int m = 0; m < 9; ++m) (&leaf9[9 * (size_t)k + m].x)[i] = comp9[m];
-                    }
-                if (!sah) gp->pair_depth = height + 1;
-                pair_root_ref = sah ? 0 : ref(0);
-                pair_root_lo = make_float4(nodes[0].lo.x, nodes[0].lo.y, nodes[0].lo.z, 0.f);
-                pair_root_hi = make_float4(nodes[0].hi.x, nodes[0].hi.y, nodes[0].hi.z, node_aux[0].y);
-                pair_count = P;
-                // stack entries: as few ref bits as the P + L refs need, the rest for the cull T
-                int rb = 2;
-                while (((int64_t)1 << rb) < (int64_t)P + L) ++rb;
-                pair_ref_shift = 32 - rb;
-            }
-        }
-        gp->bvh_lds = (size_t)gp->stack_depth * BLOCK * sizeof(int);
-    }
-    // naive mesh mode: the three positions of every triangle in ARRAY order (k_naive_mesh forms the
-    // edges tri_test() forms when it stages a tile), record k naming triangle k, and the cold data
-    std::vector<DevTriHot> naive_hot;
-    if (naive && s->num_triangles > 0) {
-        naive_hot.resize(s->num_triangles);
-        for (int k = 0; k < s->num_triangles; ++k) {
-            const pt_triangle& t = s->triangles[k];
-            float fk;
-            memcpy(&fk, &k, 4);
-            naive_hot[k].a = make_float4(t.v1.position.x, t.v1.position.y, t.v1.position.z, t.v2.position.x);
-            naive_hot[k].b = make_float4(t.v2.position.y, t.v2.position.z, t.v3.position.x, t.v3.position.y);
-            naive_hot[k].c = make_float4(t.v3.position.z, fk, 0.f, 0.f);
-        }
-        RC(fill_cold(s, cold));
-    }
-    for (int i = 0; i < s->num_geoms; ++i)
-        if (s->geoms[i].materialid < 0 || s->geoms[i].materialid >= std::max(1, s->num_materials))
-            return fail(PT_E_INVALID, "geom %d material %d out of range", i, s->geoms[i].materialid);
+    gp->has_bvh = L.has_bvh;
+    gp->stack_depth = L.stack_depth;
+    gp->pair_depth = L.pair_depth;
+    if (gp->has_bvh) gp->bvh_lds = (size_t)gp->stack_depth * BLOCK * sizeof(int);
     // VAR_BVH_SPLIT needs the pair layout, the fast traversal and an LDS geom table
-    gp->split = gp->has_bvh && !pairs.empty() && o.pipeline == PT_PIPELINE_FUSED && (o.variant & VAR_BVH_SPLIT) &&
+    gp->split = gp->has_bvh && !L.pairs.empty() && o.pipeline == PT_PIPELINE_FUSED && (o.variant & VAR_BVH_SPLIT) &&
               (o.variant & VAR_BVH_FAST) && (o.variant & (VAR_CAND_QUEUE | VAR_WAVE_REDIST)) &&
               s->num_geoms <= LDS_GEOMS;
     // MATERIAL_SORTING on the fused pipeline: the block-local regrouping by material (VAR_MAT_GROUP;
@@ -3585,53 +2917,24 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     }
     if ((int64_t)gp->local_pixels * gp->batch > (1 << 28)) return fail(PT_E_UNSUPPORTED, "wavefront too large");
 
-    RC(dalloc(&gp->d_geoms, geoms.size()));
-    RC(dalloc(&gp->d_mats, mats.size()));
-    RC(upload(gp->d_geoms, geoms.data(), geoms.size()));
-    RC(dalloc(&gp->d_cull, culls.size()));
-    // the pre-test's candidate table, for scenes whose flat pre-test is long (A/B: PT_GRID=0 off,
-    // PT_GRID=1 also for scenes under GRID_MIN_GEOMS)
-    std::vector<unsigned long long> grid;
-    float grid_lo[3] = {0.f, 0.f, 0.f}, grid_inv[3] = {0.f, 0.f, 0.f};
-    {
-        const int grid_env = gp->tune.grid;
-        const int grid_min = grid_env == 1 ? 2 : GRID_MIN_GEOMS;
-        if (grid_env != 0 && s->num_geoms >= grid_min && s->num_geoms <= LDS_GEOMS &&
-            build_candidate_table(culls, s->num_geoms, s->camera.position, grid, grid_lo, grid_inv)) {
-            RC(dalloc(&gp->d_grid, grid.size()));
-            RC(upload(gp->d_grid, grid.data(), grid.size()));
-        }
-    }
-    RC(upload(gp->d_cull, culls.data(), culls.size()));
-    RC(upload(gp->d_mats, mats.data(), mats.size()));
-    if (gp->has_bvh) {
-        RC(dalloc(&gp->d_nodes, nodes.size()));
-        RC(dalloc(&gp->d_node_aux, node_aux.size()));
-        RC(upload(gp->d_node_aux, node_aux.data(), node_aux.size()));
-        RC(dalloc(&gp->d_hot, hot.size()));
-        RC(dalloc(&gp->d_cold, cold.size()));
-        RC(upload(gp->d_nodes, nodes.data(), nodes.size()));
-        RC(upload(gp->d_hot, hot.data(), hot.size()));
-        RC(upload(gp->d_cold, cold.data(), cold.size()));
-        if (!pairs.empty()) {
-            RC(dalloc(&gp->d_pairs, pairs.size()));
-            RC(upload(gp->d_pairs, pairs.data(), pairs.size()));
-            RC(dalloc(&gp->d_hot4, hot4.size()));
-            RC(upload(gp->d_hot4, hot4.data(), hot4.size()));
-            RC(dalloc(&gp->d_leaf9, leaf9.size()));
-            RC(upload(gp->d_leaf9, leaf9.data(), leaf9.size()));
-            if (!quads.empty()) {
-                RC(dalloc(&gp->d_quads, quads.size()));
-                RC(upload(gp->d_quads, quads.data(), quads.size()));
-            }
-        }
-    }
-    if (!naive_hot.empty()) {
-        RC(dalloc(&gp->d_naive_hot, naive_hot.size()));
-        RC(upload(gp->d_naive_hot, naive_hot.data(), naive_hot.size()));
-        RC(dalloc(&gp->d_cold, cold.size()));
-        RC(upload(gp->d_cold, cold.data(), cold.size()));
-    }
+    // ---- one device buffer per vector the layout filled ----
+    auto to_device = [](auto** d, const auto& h) {
+        RC(dalloc(d, h.size()));
+        return upload(*d, h.data(), h.size());
+    };
+    RC(to_device(&gp->d_geoms, L.geoms));
+    RC(to_device(&gp->d_cull, L.culls));
+    RC(to_device(&gp->d_mats, L.mats));
+    RC(to_device(&gp->d_grid, L.grid));
+    RC(to_device(&gp->d_nodes, L.nodes));
+    RC(to_device(&gp->d_node_aux, L.node_aux));
+    RC(to_device(&gp->d_hot, L.hot));
+    RC(to_device(&gp->d_cold, L.cold));
+    RC(to_device(&gp->d_pairs, L.pairs));
+    RC(to_device(&gp->d_hot4, L.hot4));
+    RC(to_device(&gp->d_leaf9, L.leaf9));
+    RC(to_device(&gp->d_quads, L.quads));
+    RC(to_device(&gp->d_naive_hot, L.naive_hot));
     // textures (pathtrace.cu:169-201): RGBA8 texels of every texture in one buffer
     int num_tex = 0;
     if (s->num_textures > 0 && s->textures) {
@@ -3696,22 +2999,22 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     sc.pairs = gp->d_pairs;
     sc.hot4 = gp->d_hot4;
     sc.leaf9 = gp->d_leaf9;
-    sc.num_pairs = pair_count;
+    sc.num_pairs = L.pair_count;
     sc.quads = gp->split ? gp->d_quads : nullptr;   // the 4-wide records serve the traversal kernels only
-    sc.num_quads = (int)(quads.size() / 8);
-    sc.root_ref = pair_root_ref;
-    sc.ref_shift = pair_ref_shift;
-    sc.root_lo = pair_root_lo;
-    sc.root_hi = pair_root_hi;
+    sc.num_quads = (int)(L.quads.size() / 8);
+    sc.root_ref = L.root_ref;
+    sc.ref_shift = L.ref_shift;
+    sc.root_lo = L.root_lo;
+    sc.root_hi = L.root_hi;
     // node_aux's c = 64 2^-24 sx^2 / 1e-5, stored x 1.01, and cE = c x extent x 1.01: the same
     // bounds from s = sx on the device, rounded up
     sc.cull_c0 = (float)(64.0 * std::ldexp(1.0, -24) / 1e-5 * 1.01 * (1.0 + 1e-5));
-    sc.cull_E = (float)(cull_extent * (1.0 + 1e-5));
+    sc.cull_E = (float)(L.cull_extent * (1.0 + 1e-5));
     sc.grid = gp->d_grid;
     sc.grid_all = s->num_geoms >= 64 ? ~0ull : ((1ull << s->num_geoms) - 1);
     for (int a = 0; a < 3; ++a) {
-        sc.grid_lo[a] = grid_lo[a];
-        sc.grid_inv[a] = grid_inv[a];
+        sc.grid_lo[a] = L.grid_lo[a];
+        sc.grid_inv[a] = L.grid_inv[a];
     }
     RC(ensure_frames(1));            // one frame's wavefront now; larger passes grow it on first use
     gp->inited = true;

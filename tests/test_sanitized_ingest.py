@@ -74,6 +74,8 @@ def test_every_repository_scene_and_texture(driver):
     res = _run(driver, "scene", scenes)
     loaded = [n for n, r in res.items() if r.startswith("scene rc=0")]
     assert "cornell.json" in loaded and "cornell_obj_bnnuy.json" in loaded and "cornell_obj_khaslana.json" in loaded
+    for n in loaded:   # and pt_init's device scene layout (host/scene_layout.cpp) builds for each of them
+        assert " layout=0 " in res[n], (n, res[n])
     for n, r in res.items():   # the refusals are the reference's: absent OBJs, sphere.json's APERTURE
         if r.startswith("scene rc=-1"):
             assert "Failed to load" in r or "APERTURE" in r, (n, r)
