@@ -19,20 +19,28 @@
  *     layouts: pinned bit-exactly against the reference's own sources, compiled in place with
  *     g++ and the CUDA runtime headers this image ships (oracle/ref_pins/ref_harness.cpp ->
  *     tests/golden/ref_pin.json, tests/test_ref_pins.py).
- *   - src/interactions.cu (scatterRay and the BSDFs) needs thrust/random.h, which only rocThrust
- *     provides here and which clashes with the CUDA vector types: UNBUILDABLE.  Pinned
- *     statistically instead: the GPU (bit-exact with this oracle in trig_mode 1) renders ten of
- *     the reference authors' own committed 800x800 renders to within 0.16-0.22/255 mean tile
- *     difference (tests/test_ref_renders.py; the sweep of every image against every scene variant
- *     is tests/golden/ref_render_sweep.json): the diffuse branch (interactions.cu:92-108), the
- *     mirror branch (:111-118, :465-470: cornell_multiple_glass's reflective cube), transmissive
- *     (:146-168), glass + Fresnel (:173-235) and the aperture sample (pathtrace.cu:231-237); and the
- *     known answers SURVEY.md §8a records from a run of the reference (cornell per-bounce
- *     live-path counts, glass-scene segment total, first NaN pixel) match exactly
- *     (tests/test_oracle_pins.py).  The Cook-Torrance / microfacet branch (interactions.cu:238-435,
- *     :481-525) matches NO reference-held image (best mean tile difference 17-25/255 with the
- *     camera refitted): PARITY UNPINNED for it beyond this restatement.  Bit-level BSDF parity:
- *     unpinned.
+ *   - src/interactions.cu + interactions.h (scatterRay and every BSDF helper, :7-542): pinned
+ *     bit-exactly against the reference's own source, compiled in place as host C++ with g++
+ *     (oracle/ref_pins/bsdf_pin.cpp -> tests/golden/bsdf_pin.npz, tests/test_bsdf_pin.py).  Its
+ *     thrust/random.h is our stand-in (oracle/ref_pins/thrust_standin/, minstd +
+ *     uniform_real_distribution<float>), which reproduces tests/golden/rng_pin.json, i.e. rocThrust.
+ *     The fixture's ~3900 records per mode sit on the edges (degenerate, non-unit and NaN normals,
+ *     coordinateSystem's tie, grazing and back-facing directions, the critical angle ulp by ulp,
+ *     seeds whose draw is exactly 0, exactly 1 or next to Fprob, pdf == 0, inf / NaN throughput);
+ *     or_scatter / or_shade (trig_mode 0, arg_order 0) equal it on every finite bit, for all five
+ *     material classes, Cook-Torrance included.  The HIP kernel is checked against the same fixture
+ *     directly for the classes without sin / cos / powf (mirror, transmissive, glass) and through
+ *     trig_mode 1 for the others, whose distance to the fixture is measured.
+ *   - Still unpinned at the bit level: textured and bump-mapped shading (tex2D has no host build;
+ *     the framework defines that fetch itself, include/pt/pt_texture.h), sampleAperture, and the
+ *     __global__ kernel bodies of pathtrace.cu, which are restated (the harnesses say which lines).
+ *     They stand on the statistical pins: the GPU renders ten of the reference authors' committed
+ *     800x800 renders to within 0.16-0.22/255 mean tile difference (tests/test_ref_renders.py,
+ *     tests/golden/ref_render_sweep.json), and the known answers SURVEY.md §8a records from a run
+ *     of the reference (cornell per-bounce live-path counts, glass-scene segment total, first NaN
+ *     pixel) match exactly (tests/test_oracle_pins.py).  The Cook-Torrance code is now pinned, but
+ *     its three reference images still match no scene file we hold (best mean tile difference
+ *     17-25/255 with the camera refitted).
  *
  * Layouts are the reference's own (include/pt/scene_structs.h): AoS PathSegment /
  * ShadeableIntersection, exactly as pathtrace.cu holds them.

@@ -207,3 +207,69 @@ def png_input_large():
     noise = _u(5, w * h, 1).reshape(h, w) * np.float32(0.4)
     img = np.stack([r + noise * (y > 100), g, b], axis=-1).astype(np.float32).reshape(-1, 3)
     return w, h, 5, img
+
+
+# ---------------------------------------------------------------------------------------------
+# BSDF pin (oracle/ref_pins/bsdf_pin.cpp -> tests/golden/bsdf_pin.npz, tests/test_bsdf_pin.py)
+# ---------------------------------------------------------------------------------------------
+# the nine Material fields scatterRay reads, in sceneStructs.h order
+BSDF_MAT_FIELDS = ("color_r", "color_g", "color_b", "hasReflective", "hasRefractive", "roughness", "metallic",
+                   "indexOfRefraction", "emittance")
+P_SCATTER_IN = np.dtype([("material", "<f4", (9,)), ("path", P_PATH), ("intersect",) + V3, ("normal",) + V3,
+                         ("iter", "<i4")])
+P_SHADE_IN = np.dtype([("isect", P_ISECT), ("path", P_PATH), ("iter", "<i4")])
+BSDF_ITERS = (1, 9, 5000)
+BSDF_CLASSES = ("diffuse", "reflective", "transmissive", "glass", "microfacet")
+DIFFUSE, REFLECTIVE, TRANSMISSIVE, GLASS, MICROFACET = range(5)
+
+
+def bsdf_class(mat: np.ndarray) -> np.ndarray:
+    """scatterRay's branch (interactions.cu:455-528) for (n, 9) material rows."""
+    mat = np.asarray(mat, np.float32).reshape(-1, 9)
+    refl, refr, rough, metal = mat[:, 3] > 0, mat[:, 4] > 0, mat[:, 5] >= 0, mat[:, 6] >= 0
+    return np.where(refl & refr, GLASS, np.where(refl, REFLECTIVE, np.where(refr, TRANSMISSIVE, np.where(
+        rough & metal, MICROFACET, DIFFUSE)))).astype(np.uint8)
+
+
+RNG_M, RNG_A = 2147483647, 48271
+
+
+def utilhash(a: np.ndarray) -> np.ndarray:
+    """intersections.h:13-22 on uint32 arrays."""
+    a = np.asarray(a).astype(np.uint32)
+    u = np.uint32
+    a = (a + u(0x7ED55D16)) + (a << u(12))
+    a = (a ^ u(0xC761C23C)) ^ (a >> u(19))
+    a = (a + u(0x165667B1)) + (a << u(5))
+    a = (a + u(0xD3A2646C)) ^ (a << u(9))
+    a = (a + u(0xFD7046C5)) + (a << u(3))
+    a = (a ^ u(0xB55A4F09)) ^ (a >> u(16))
+    return a
+
+
+def rng_state(iteration, index, depth) -> np.ndarray:
+    """Engine state after makeSeededRandomEngine(iter, index, depth) (pathtrace.cu:51-56), uint64."""
+    with np.errstate(over="ignore"):
+        key = (np.uint32(0x80000000) | (np.asarray(depth).astype(np.uint32) << np.uint32(22))
+               | np.asarray(iteration).astype(np.uint32))
+        h = utilhash(key) ^ utilhash(np.asarray(index).astype(np.uint32))
+    x = h.astype(np.uint64) % np.uint64(RNG_M)
+    return np.where(x == 0, np.uint64(1), x)
+
+
+def rng_draw(state: np.ndarray, j: int):
+    """(engine value, u01 float) of the j-th draw (j >= 1) from `state`."""
+    x = (np.asarray(state, np.uint64) * np.uint64(pow(RNG_A, j, RNG_M))) % np.uint64(RNG_M)
+    u = (x - np.uint64(1)).astype(np.float32) / np.float32(2147483648.0)
+    return x, u
+
+
+def bsdf_shade_inputs(fx) -> np.ndarray:
+    """The `shade` input records of tests/golden/bsdf_pin.npz: path, normal and iteration of the
+    scatter record `shade_index` names, plus that record's own t and scene material id."""
+    src = fx["scatter_in"][fx["shade_index"]]
+    sh = np.zeros(len(src), P_SHADE_IN)
+    sh["path"], sh["iter"] = src["path"], src["iter"]
+    sh["isect"]["t"], sh["isect"]["materialId"] = fx["shade_t"], fx["shade_material"]
+    sh["isect"]["surfaceNormal"] = src["normal"]
+    return sh
