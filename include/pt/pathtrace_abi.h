@@ -249,6 +249,25 @@ int32_t pt_test_shade(int32_t iteration, const pt_shadeable_isect* isects, pt_pa
 /* stable partition of n paths on remainingBounces > 0 -> out (alive first, in order);
  * returns the alive count through *alive */
 int32_t pt_test_compact(const pt_path_segment* paths, int64_t n, pt_path_segment* out, int64_t* alive);
+/* one bounce (>= 1) of the FUSED pipeline, launched exactly as a frame launches it (the context's
+ * kernel variant, with its traversal-queue, hand-over and shading kernels), on n caller paths laid
+ * into that bounce's input segments: seg_counts[8] consecutive paths per segment (NULL: all in
+ * segment 0).  A single-frame pass of `iteration`.  Terminated paths are added into the accumulated
+ * image as in a frame; the survivors come back in out_paths, segment after segment, in no
+ * particular order inside a segment: *n_out of them, seg_out[s] (8 entries, may be NULL) from
+ * segment s.  PT_E_INVALID: n above one frame's paths, a segment count above what a segment holds,
+ * bounce outside 1 .. 63, the staged pipeline, more survivors than out_capacity. */
+int32_t pt_test_bounce(int32_t iteration, int32_t bounce, const pt_path_segment* paths, int64_t n,
+                       const int32_t* seg_counts, pt_path_segment* out_paths, int64_t out_capacity, int64_t* n_out,
+                       int32_t* seg_out);
+/* the fused-kernel variant (pt_options.variant bits) the later bounces of this context really
+ * launch, after pt_init resolved material grouping, the texture-free build and the traversal layout;
+ * *split != 0: mesh rays go through the traversal queue to k_bvh_bounce.  PT_E_INVALID: staged */
+int32_t pt_test_bounce_variant(int32_t* variant, int32_t* split);
+/* the candidate table of the current context (scenes of 16 .. 64 geoms): an origin's cell is
+ * floor((o - lo) * inv) per axis, `cells` cells per axis, `bins` direction bins per ratio;
+ * cells = 0 when the scene has no table */
+int32_t pt_test_grid_info(float lo[3], float inv[3], int32_t* cells, int32_t* bins);
 /* stable sort of n (isect, path) pairs by materialId -> permutation perm[n] */
 int32_t pt_test_sort(const pt_shadeable_isect* isects, int64_t n, int32_t* perm);
 /* first n draws of makeSeededRandomEngine(iter, index, depth) for m seeds -> out[m*n] */

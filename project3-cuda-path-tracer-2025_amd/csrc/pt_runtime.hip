@@ -433,8 +433,12 @@ __global__ __launch_bounds__(BLOCK) void k_bounce(SceneDev sc, PathBuf in, PathB
         if (live) shade_path<(VAR & VAR_NO_TEX) == 0>(sc, p, h, iter + p.slot, [&]() { return hit_attr(sc, h); });
     }
     if (TIMING && active) tc = sec_clock();
-    const bool surv = active && !queued && p.rb > 0;
-    if (active && !queued && !surv) gather_into_image(image, sc, to_plane, p);
+    // later bounces: a path that came in with remainingBounces <= 0 was gathered when it terminated
+    // (pathtrace.cu:535-537 skips it) -- it neither survives nor adds its colour again.  The camera
+    // bounce gathers every path it made (trace depth 0: the untouched camera colour).
+    const bool mine = FIRST ? active : live;
+    const bool surv = mine && !queued && p.rb > 0;
+    if (mine && !queued && !surv) gather_into_image(image, sc, to_plane, p);
     const int lane = tid & 63;
     const int seg = blockIdx.x & (NSEG - 1);
     if (VAR & VAR_WAVE_ATOMIC) {
@@ -2353,19 +2357,22 @@ void soa_to_paths(const std::vector<float4>& A, const std::vector<float4>& B, co
     }
 }
 
-int upload_paths(int buf, const pt_path_segment* paths, int64_t n) {
+// n paths to / from slots at .. at + n - 1 of path buffer `buf`
+int upload_paths(int buf, const pt_path_segment* paths, int64_t n, int64_t at = 0) {
+    if (n <= 0) return PT_OK;
     std::vector<float4> A, B, C;
     paths_to_soa(paths, n, A, B, C);
-    HIPCHK(smemcpy(gp->d_path[buf][0], A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(smemcpy(gp->d_path[buf][1], B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(smemcpy(gp->d_path[buf][2], C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(smemcpy(gp->d_path[buf][0] + at, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(smemcpy(gp->d_path[buf][1] + at, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(smemcpy(gp->d_path[buf][2] + at, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
     return PT_OK;
 }
-int download_paths(int buf, int64_t n, pt_path_segment* out) {
+int download_paths(int buf, int64_t n, pt_path_segment* out, int64_t at = 0) {
+    if (n <= 0) return PT_OK;
     std::vector<float4> A(n), B(n), C(n);
-    HIPCHK(smemcpy(A.data(), gp->d_path[buf][0], n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(smemcpy(B.data(), gp->d_path[buf][1], n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(smemcpy(C.data(), gp->d_path[buf][2], n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(smemcpy(A.data(), gp->d_path[buf][0] + at, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(smemcpy(B.data(), gp->d_path[buf][1] + at, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(smemcpy(C.data(), gp->d_path[buf][2] + at, n * sizeof(float4), hipMemcpyDeviceToHost));
     soa_to_paths(A, B, C, n, out);
     return PT_OK;
 }
@@ -3674,6 +3681,113 @@ int32_t pt_test_compact(const pt_path_segment* paths, int64_t n, pt_path_segment
     release_graph();
     RC(download_paths(1, na, out));
     RC(ctl_reset());
+    return PT_OK;
+}
+
+// One production bounce of the fused pipeline on caller-supplied paths: the n paths laid into the
+// input buffer of `bounce` as the previous bounce's kernels would have left them (seg_counts[s] of
+// them in segment s, in order; NULL: all in segment 0), a single-frame pass of `iteration` in
+// frame slot 0, then launch_bounce exactly as enqueue_pass_body calls it.  Terminated paths are
+// gathered into the accumulated image; the survivors of every output segment come back segment
+// after segment (their order inside a segment is the kernels' business), seg_out[s] of them from
+// segment s.  The path buffers are sized for min(frames per pass, NSEG) frames first: with NSEG
+// frames a segment holds a whole frame's paths, so any split of n over the segments fits.
+int32_t pt_test_bounce(int32_t iteration, int32_t bounce, const pt_path_segment* paths, int64_t n,
+                       const int32_t* seg_counts, pt_path_segment* out_paths, int64_t out_capacity, int64_t* n_out,
+                       int32_t* seg_out) {
+    RC(need_init());
+    RC(need_single("pt_test_bounce"));
+    if (gp->opts.pipeline != PT_PIPELINE_FUSED || gp->naive)
+        return fail(PT_E_INVALID, "pt_test_bounce: the fused pipeline only (this context runs the staged one)");
+    if (iteration <= 0) return fail(PT_E_INVALID, "iteration is 1-based, got %d", iteration);
+    if (bounce < 1 || bounce >= MAXB)
+        return fail(PT_E_INVALID, "pt_test_bounce: bounce must be 1 .. %d, got %d", MAXB - 1, bounce);
+    if (n < 0 || n > gp->local_pixels)
+        return fail(PT_E_INVALID, "pt_test_bounce: n = %lld, one frame's wavefront holds %d paths", (long long)n,
+                    gp->local_pixels);
+    if ((n > 0 && !paths) || !n_out || (out_capacity > 0 && !out_paths) || out_capacity < 0)
+        return fail(PT_E_INVALID, "pt_test_bounce: null argument");
+    RC(ensure_test_paths(n));
+    RC(ensure_frames(std::min(gp->batch, NSEG)));
+    const int stride = gp->seg_stride;
+    int cnt[NSEG] = {};
+    int64_t total = 0;
+    for (int s = 0; s < NSEG; ++s) {
+        cnt[s] = seg_counts ? seg_counts[s] : (s == 0 ? (int)n : 0);
+        if (cnt[s] < 0 || cnt[s] > stride)
+            return fail(PT_E_INVALID, "pt_test_bounce: %d paths in segment %d, a segment holds %d", cnt[s], s, stride);
+        total += cnt[s];
+    }
+    if (total != n) return fail(PT_E_INVALID, "pt_test_bounce: the segment counts add up to %lld, n = %lld",
+                                (long long)total, (long long)n);
+    HIPCHK(hipStreamSynchronize(gp->stream));
+    RC(ctl_reset());   // every counter zero: this bounce's queue, the next bounce's segments
+    const int ib = bounce & 1, ob = (bounce + 1) & 1;
+    int64_t at = 0;
+    for (int s = 0; s < NSEG; ++s) {
+        RC(upload_paths(ib, paths + at, cnt[s], (int64_t)s * stride));
+        HIPCHK(smemcpy(&gp->d_ctl->cnt[bounce][s][0], &cnt[s], sizeof(int), hipMemcpyHostToDevice));
+        at += cnt[s];
+    }
+    const int head[3] = {iteration, 1, 0};   // FrameCtl::iter, batch, plane
+    HIPCHK(smemcpy(&gp->d_ctl->iter, head, sizeof head, hipMemcpyHostToDevice));
+    if (n > 0) {
+        launch_bounce(false, gp->has_bvh, gp->opts.variant & ~VAR_BVH_NODES, dim3(nblocks((int)n)), pathbuf(ib),
+                      pathbuf(ob), bounce);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(gp->stream));
+    int got[NSEG] = {};
+    total = 0;
+    for (int s = 0; s < NSEG; ++s) {
+        HIPCHK(smemcpy(&got[s], &gp->d_ctl->cnt[bounce + 1][s][0], sizeof(int), hipMemcpyDeviceToHost));
+        total += got[s];
+    }
+    release_graph();
+    for (int s = 0; s < NSEG; ++s)
+        if (got[s] < 0 || got[s] > stride) {
+            RC(ctl_reset());
+            return fail(PT_E_HIP, "pt_test_bounce: output segment %d counts %d paths, it holds %d", s, got[s], stride);
+        }
+    *n_out = total;
+    if (total > out_capacity) {
+        RC(ctl_reset());
+        return fail(PT_E_INVALID, "pt_test_bounce: %lld survivors, room for %lld", (long long)total,
+                    (long long)out_capacity);
+    }
+    at = 0;
+    for (int s = 0; s < NSEG; ++s) {
+        RC(download_paths(ob, got[s], out_paths + at, (int64_t)s * stride));
+        if (seg_out) seg_out[s] = got[s];
+        at += got[s];
+    }
+    RC(ctl_reset());
+    return PT_OK;
+}
+
+// the kernel variant pt_test_bounce (and every later bounce of a frame) launches: launch_bounce's own
+// effective_variant of the context's options; *split: k_bvh_bounce runs behind the traversal queue
+int32_t pt_test_bounce_variant(int32_t* variant, int32_t* split) {
+    RC(need_init());
+    if (!variant || !split) return fail(PT_E_INVALID, "pt_test_bounce_variant: null argument");
+    if (gp->opts.pipeline != PT_PIPELINE_FUSED || gp->naive)
+        return fail(PT_E_INVALID, "pt_test_bounce_variant: the fused pipeline only (this context runs the staged one)");
+    *variant = effective_variant(false, gp->opts.variant & ~VAR_BVH_NODES);
+    *split = (gp->has_bvh && (*variant & VAR_BVH_SPLIT)) ? 1 : 0;
+    return PT_OK;
+}
+
+// the candidate table's geometry (grid_superset): cell = (o - lo) * inv per axis, `cells` cells per
+// axis and `bins` direction bins per ratio; cells = 0: this context's scene has no table
+int32_t pt_test_grid_info(float lo[3], float inv[3], int32_t* cells, int32_t* bins) {
+    RC(need_init());
+    if (!lo || !inv || !cells || !bins) return fail(PT_E_INVALID, "pt_test_grid_info: null argument");
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = gp->sc.grid_lo[a];
+        inv[a] = gp->sc.grid_inv[a];
+    }
+    *cells = gp->sc.grid ? GRID_G : 0;
+    *bins = GRID_B;
     return PT_OK;
 }
 

@@ -99,7 +99,7 @@ ABI_SYMBOLS = [
     "pt_debug_section_counters", "pt_texture_load",
     "pt_save_png", "pt_scene_load_ex", "pt_bvh_build", "pt_bvh_build_last_error", "pt_test_shade", "pt_test_compact", "pt_test_sort", "pt_test_rng", "pt_test_pbo", "pt_profile_frames", "pt_prepare_frames",
     "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_set_trace_depth", "pt_set_speculation",
-    "pt_debug_spec_counts",
+    "pt_debug_spec_counts", "pt_test_bounce", "pt_test_grid_info", "pt_test_bounce_variant",
 ]
 # include/pt/pt_viewer.h (the headless interactive viewer)
 VIEWER_SYMBOLS = [
@@ -135,7 +135,8 @@ def _load():
         "pt_scene_last_error": (ctypes.c_char_p, []),
         "pt_test_camera": (i32, [i32, vp, i64]), "pt_test_intersect": (i32, [vp, i64, vp]),
         "pt_test_shade": (i32, [i32, vp, vp, i64]), "pt_test_compact": (i32, [vp, i64, vp, vp]),
-        "pt_test_sort": (i32, [vp, i64, vp]), "pt_test_rng": (i32, [vp, i64, i32, vp]),
+        "pt_test_sort": (i32, [vp, i64, vp]), "pt_test_bounce": (i32, [i32, i32, vp, i64, vp, vp, i64, vp, vp]),
+        "pt_test_grid_info": (i32, [vp, vp, vp, vp]), "pt_test_bounce_variant": (i32, [vp, vp]), "pt_test_rng": (i32, [vp, i64, i32, vp]),
         "pt_test_pbo": (i32, [vp, i64, i32, vp]), "pt_profile_frames": (i32, [i32, i32, vp]), "pt_prepare_frames": (i32, [i32]),
         "pt_debug_section_counters": (i32, [vp, i32, i32]),
         "pt_texture_load": (i32, [ctypes.c_char_p, vp, vp, vp, i64]),
@@ -516,6 +517,37 @@ class PathTracer:
         perm = np.zeros(len(isects), np.int32)
         _check(lib.pt_test_sort(_ptr(isects), len(isects), _ptr(perm)), "pt_test_sort")
         return perm
+
+    def test_bounce(self, iteration: int, paths: np.ndarray, bounce: int = 1, seg_counts=None):
+        """One bounce of the fused pipeline on `paths` (pt_test_bounce): (survivors, seg_out).  Terminated
+        paths are added into the accumulated image.  seg_counts: paths per input segment (8 entries;
+        None: all in segment 0); seg_out: survivors per output segment."""
+        paths = np.ascontiguousarray(paths, PATH)
+        seg = None if seg_counts is None else np.ascontiguousarray(seg_counts, np.int32)
+        if seg is not None and seg.shape != (8,):
+            raise ValueError("seg_counts: 8 entries")
+        out = np.zeros(len(paths), PATH)
+        seg_out = np.zeros(8, np.int32)
+        n_out = ctypes.c_int64()
+        _check(lib.pt_test_bounce(int(iteration), int(bounce), _ptr(paths), len(paths), _ptr(seg), _ptr(out), len(out),
+                                  ctypes.byref(n_out), seg_out.ctypes.data), "pt_test_bounce")
+        return out[:n_out.value], seg_out
+
+    def bounce_variant(self) -> tuple:
+        """(variant bits the later bounces' k_bounce really runs, mesh rays take the split queue) of this
+        context (pt_test_bounce_variant)."""
+        v, sp = ctypes.c_int32(), ctypes.c_int32()
+        _check(lib.pt_test_bounce_variant(ctypes.byref(v), ctypes.byref(sp)), "pt_test_bounce_variant")
+        return v.value, bool(sp.value)
+
+    def grid_info(self) -> dict:
+        """The candidate table of this context (pt_test_grid_info): {"lo", "inv", "cells", "bins"};
+        cells == 0: the scene has no table."""
+        lo, inv = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        cells, bins = ctypes.c_int32(), ctypes.c_int32()
+        _check(lib.pt_test_grid_info(lo.ctypes.data, inv.ctypes.data, ctypes.byref(cells), ctypes.byref(bins)),
+               "pt_test_grid_info")
+        return {"lo": lo, "inv": inv, "cells": cells.value, "bins": bins.value}
 
     def free(self):
         lib.pt_free()
