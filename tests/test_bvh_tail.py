@@ -1,4 +1,4 @@
-"""Handed-over traversals (k_bvh_bounce -> k_bvh_tail_trav -> k_bvh_tail_shade, pt_runtime.hip).
+"""Handed-over traversals (k_bvh_bounce -> k_bvh_tail_trav -> k_bvh_tail_shade, csrc/pt_pass_kernels.h).
 
 Once no more than PT_BVH_TAIL_LANES lanes of a traversal wave are still traversing, those rays'
 traversal state (best hit, next node, stack) is written out; k_bvh_tail_trav resumes them in waves

@@ -1,7 +1,7 @@
 """Ray-level probes of the FUSED pipeline's bounce kernels — needs an MI355X.
 
 PathTracer.test_bounce (pt_test_bounce) lays caller paths into a bounce's input segments and runs
-launch_bounce exactly as a frame does: k_bounce with the context's variant (block_intersect /
+launch_bounce (csrc/rt_pass.h) exactly as a frame does: k_bounce with the context's variant (block_intersect /
 wave_intersect / intersect_scene_q, the candidate table, material grouping) and, in mesh scenes,
 k_bvh_bounce -> k_bvh_tail_trav -> k_bvh_tail_shade behind the split queue.  Frames only ever feed
 these kernels rays that start at the camera or on a surface inside the room; here they get

@@ -1,4 +1,4 @@
-"""pathtrace()'s next-frame speculation (pt_runtime.hip spec_*).
+"""pathtrace()'s next-frame speculation (csrc/rt_spec.h spec_*).
 
 main.cpp calls pathtrace(pbo, frame, ++iteration) once per frame and the reference copies the
 accumulated image to host memory every call (pathtrace.cu:783).  After tracing frame N the library

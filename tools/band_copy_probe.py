@@ -1,7 +1,7 @@
 """What one shard's host copy costs on its own PCIe link (tools only; one GPU).
 
 pathtrace() copies the 800x800 float3 image (7.68 MB) to pageable host memory every call.  With
-N devices each shard copies only its own interleaved row bands (pt_runtime.hip band_prepare: one
+N devices each shard copies only its own interleaved row bands (csrc/rt_multi.h band_prepare over host/band_layout.h: one
 hipMemcpy2DAsync of bands of 8 rows, N bands apart).  On an N-GPU node each shard has a link of
 its own, so a call's copy costs what ONE shard's band copy costs alone; this box has one GPU and
 one link, so that is what is timed here: the whole image as one copy, then shard 0's bands for
