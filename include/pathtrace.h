@@ -23,6 +23,12 @@ void pathtraceSetOptions(const pt_options& opts);
 // image itself is untouched.
 void pathtraceDenoise(float* out);
 
+// Framework addition: pathtraceDenoise with the temporal stage of pt/pt_denoise_temporal.h in front
+// (default parameters): the history of the earlier calls is reprojected through camera changes and
+// a per-pixel variance guides the filter.  The feature buffer is captured when the camera changed
+// since the last call; pathtraceInit / pathtraceFree drop the history.
+void pathtraceDenoiseTemporal(float* out);
+
 // Framework addition: the reference's NAIVE_MESH_LOADING switch (pathtrace.cu:365-393) at run time,
 // pt_set_naive_mesh of pt/pt_naive_mesh.h: every triangle in array order, no BVH.  Takes effect at
 // the next pathtraceInit; options set through pathtraceSetOptions must then ask for

@@ -6,6 +6,9 @@
 //   k_atrous    one level of the filter: 5 x 5 taps at step s, weights from colour, normal and
 //               position; steps 1 and 2 stage the block's tile + halo in LDS, steps >= 4 read
 //               their (strided) taps directly, a tap row's loads issued together
+//   k_atrous_*_var  the same levels with the colour term normalised by the centre pixel's
+//               variance (include/pt/pt_denoise_temporal.h, stage 3): the bodies are templates on
+//               the argument struct, and only the centre's colour factor differs
 //
 // The filter is defined in include/pt/pt_denoise.h; tests/test_denoise.py restates it in numpy.
 #pragma once
@@ -90,12 +93,23 @@ PT_DEV float4 at_load_color(const AtrousArgs& a, int idx, float hit) {
     return fin ? make_float4(r, g, b, 1.0f) : make_float4(0.f, 0.f, 0.f, 0.0f);
 }
 
+// the variance-guided levels: cin is the integrated colour rgb | N (N >= 1 marks a finite colour)
+struct AtrousArgsVar : AtrousArgs {
+    const float4* mom;     // mu1, mu2, variance, 0 per pixel
+    float sv2;             // (sigma_variance 2^-l)^2
+};
+
+// the centre pixel's colour factor, constant over its taps
+PT_DEV float at_kcolor(const AtrousArgs& a, int) { return a.k_color; }
+PT_DEV float at_kcolor(const AtrousArgsVar& a, int idx) { return 1.0f / (a.sv2 * (a.mom[idx].z + 1e-6f)); }
+
 struct AtrousAcc {
     float r, g, b, w;
 };
 
 // one tap: (colour | finite, normal, position | hit) of q against the centre's; hh = h[i] h[j]
-PT_DEV void at_tap(AtrousAcc& s, const AtrousArgs& a, float hh, float4 cp, float4 np, float4 xp, float4 cq,
+// kc: the centre's colour factor (at_kcolor)
+PT_DEV void at_tap(AtrousAcc& s, const AtrousArgs& a, float kc, float hh, float4 cp, float4 np, float4 xp, float4 cq,
                    float4 nq, float4 xq) {
     const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
     const float dc = cp.w > 0.5f ? (dr * dr + dg * dg) + db * db : 0.0f;   // non-finite centre: colour term 1
@@ -103,7 +117,7 @@ PT_DEV void at_tap(AtrousAcc& s, const AtrousArgs& a, float hh, float4 cp, float
     const float x0 = xp.x - xq.x, x1 = xp.y - xq.y, x2 = xp.z - xq.z;
     const float dn = (n0 * n0 + n1 * n1) + n2 * n2;   // two misses: planes hold 0, the terms are 1
     const float dx = (x0 * x0 + x1 * x1) + x2 * x2;
-    const float e = (dc * a.k_color + dn * a.k_normal) + dx * a.k_position;
+    const float e = (dc * kc + dn * a.k_normal) + dx * a.k_position;
     // outside taps carry hit flag -1 and finite flag 0; a non-finite tap's colour is stored as 0
     const bool on = xq.w == xp.w && cq.w > 0.5f;
     const float w = on ? hh * __expf(-e) : 0.0f;
@@ -154,8 +168,8 @@ PT_DEV float at_h(int i) { return i == 0 ? 0.375f : ((i == 1 || i == -1) ? 0.25f
 
 // steps 1 and 2: the tile and its halo of 2 S pixels, staged once in LDS (S = 2: 24 x 24 entries
 // of 48 B = 27 KB), every tap an LDS read
-template <int S>
-__global__ __launch_bounds__(BLOCK) void k_atrous_lds(AtrousArgs a) {
+template <int S, class Args>
+PT_DEV void atrous_lds(const Args& a) {
     constexpr int R = 2 * S, TW = AT_TILE + 2 * R;
     __shared__ float4 s_c[TW * TW], s_n[TW * TW], s_x[TW * TW];
     const int bx = blockIdx.x * AT_TILE, by = blockIdx.y * AT_TILE;
@@ -179,27 +193,34 @@ __global__ __launch_bounds__(BLOCK) void k_atrous_lds(AtrousArgs a) {
     if (x >= a.W || y >= a.H) return;
     const int lc = (ty + R) * TW + tx + R;
     const float4 cp = s_c[lc], np = s_n[lc], xp = s_x[lc];
+    const float kc = at_kcolor(a, y * a.W + x);
     AtrousAcc s{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
 #pragma unroll
         for (int i = -2; i <= 2; ++i) {
             const int l = lc + (j * TW + i) * S;
-            at_tap(s, a, at_h(i) * at_h(j), cp, np, xp, s_c[l], s_n[l], s_x[l]);
+            at_tap(s, a, kc, at_h(i) * at_h(j), cp, np, xp, s_c[l], s_n[l], s_x[l]);
         }
     }
     at_store(a, y * a.W + x, s, xp.w);
 }
+template <int S>
+__global__ __launch_bounds__(BLOCK) void k_atrous_lds(AtrousArgs a) { atrous_lds<S>(a); }
+template <int S>
+__global__ __launch_bounds__(BLOCK) void k_atrous_lds_var(AtrousArgsVar a) { atrous_lds<S>(a); }
 
 // steps >= 4: taps read directly (a halo of 2 s pixels no longer pays); the 15 loads of a tap
 // row are independent of the arithmetic before them
-__global__ __launch_bounds__(BLOCK) void k_atrous_direct(AtrousArgs a) {
+template <class Args>
+PT_DEV void atrous_direct(const Args& a) {
     const int tx = threadIdx.x % AT_TILE, ty = threadIdx.x / AT_TILE;
     const int x = blockIdx.x * AT_TILE + tx, y = blockIdx.y * AT_TILE + ty;
     if (x >= a.W || y >= a.H) return;
     const int pc = y * a.W + x;
     const float4 np = a.gn[pc], xp = a.gx[pc];
     const float4 cp = at_load_color(a, pc, xp.w);
+    const float kc = at_kcolor(a, pc);
     AtrousAcc s{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
@@ -220,10 +241,12 @@ __global__ __launch_bounds__(BLOCK) void k_atrous_direct(AtrousArgs a) {
 #pragma unroll
         for (int i = -2; i <= 2; ++i) {
             if (!in[i + 2]) cq[i + 2].w = 0.0f;
-            at_tap(s, a, at_h(i) * at_h(j), cp, np, xp, cq[i + 2], nq[i + 2], xq[i + 2]);
+            at_tap(s, a, kc, at_h(i) * at_h(j), cp, np, xp, cq[i + 2], nq[i + 2], xq[i + 2]);
         }
     }
     at_store(a, pc, s, xp.w);
 }
+__global__ __launch_bounds__(BLOCK) void k_atrous_direct(AtrousArgs a) { atrous_direct(a); }
+__global__ __launch_bounds__(BLOCK) void k_atrous_direct_var(AtrousArgsVar a) { atrous_direct(a); }
 
 }  // namespace ptd

@@ -1,5 +1,5 @@
 // rt_abi_denoise.h — the denoiser's entry points (inside pt_runtime.hip's extern "C" block).
-// Owns: pt_gbuffer_*, pt_denoise*, pt_debug_denoise_*.  Calls: rt_core.h, M.n of rt_multi.h, and
+// Owns: pt_gbuffer_* (and which of the two plane sets a capture writes), pt_denoise*, pt_debug_denoise_*.  Calls: rt_core.h, M.n of rt_multi.h, and
 // the kernels of pt_denoise_kernels.h.
 
 // ---------------------------------------------------------------------------------------------
@@ -34,11 +34,15 @@ int32_t pt_gbuffer_capture(int32_t iteration) {
     if (iteration <= 0) return fail(PT_E_INVALID, "iteration is 1-based, got %d", iteration);
     const int n = gp->pixels_total;
     gp->gbuf_valid = false;
-    if (!gp->d_gbuf[0]) {
-        for (float4*& p : gp->d_gbuf) RC(dalloc(&p, (size_t)n));
+    if (!gp->d_gbuf[0][0]) {
+        for (float4*& p : gp->d_gbuf[0]) RC(dalloc(&p, (size_t)n));
         for (float4*& p : gp->d_dn_color) RC(dalloc(&p, (size_t)n));
     }
-    const GBuf g{gp->d_gbuf[0], gp->d_gbuf[1], gp->d_gbuf[2]};
+    // the temporal history (rt_abi_temporal.h) keeps the planes of its capture: write the other set
+    if (gp->tp_history && gp->tp_hist_set == gp->gbuf_cur) gp->gbuf_cur ^= 1;
+    gp->tp_base_valid = false;
+    float4* const* cur = gp->d_gbuf[gp->gbuf_cur];
+    const GBuf g{cur[0], cur[1], cur[2]};
     if (g_dn_timing) RC(denoise_event(0));
     // the traversal pt_test_intersect (and the staged pipeline) runs for this context's options
     if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
@@ -64,7 +68,7 @@ int32_t pt_gbuffer_get(float* normal_t, float* position, float* albedo_mat, int6
                                                  (long long)n_pixels, gp->pixels_total);
     float* dst[3] = {normal_t, position, albedo_mat};
     for (int k = 0; k < 3; ++k)
-        if (dst[k]) HIPCHK(smemcpy(dst[k], gp->d_gbuf[k], sizeof(float4) * (size_t)gp->pixels_total, hipMemcpyDeviceToHost));
+        if (dst[k]) HIPCHK(smemcpy(dst[k], gp->d_gbuf[gp->gbuf_cur][k], sizeof(float4) * (size_t)gp->pixels_total, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -86,9 +90,9 @@ int32_t pt_denoise(const pt_denoise_params* params, int32_t samples, pt_uchar4* 
     auto inv_sq = [](double s) { return (float)std::min(1.0 / (s * s), 3.0e38); };
     AtrousArgs a{};
     a.image = gp->d_image;
-    a.gn = gp->d_gbuf[0];
-    a.gx = gp->d_gbuf[1];
-    a.ga = gp->d_gbuf[2];
+    a.gn = gp->d_gbuf[gp->gbuf_cur][0];
+    a.gx = gp->d_gbuf[gp->gbuf_cur][1];
+    a.ga = gp->d_gbuf[gp->gbuf_cur][2];
     a.W = gp->width;
     a.H = gp->height;
     a.demod = p.demodulate_albedo != 0;

@@ -140,11 +140,24 @@ struct State {
     int key_bits = 1;
     bool multi = false;              // a shard context of a multi-device pt_init
     // denoiser (pt/pt_denoise.h): feature planes + colour ping-pong, allocated by the first capture
-    float4* d_gbuf[3] = {nullptr, nullptr, nullptr};   // normal | t, position | hit, albedo | material
+    // two sets of planes (the second allocated by the first pt_denoise_temporal): a capture never
+    // overwrites the set the temporal history refers to; gbuf_cur is the set the last capture wrote
+    float4* d_gbuf[2][3] = {};       // normal | t, position | hit, albedo | material
+    int gbuf_cur = 0;
     float4* d_dn_color[2] = {nullptr, nullptr};
     bool gbuf_valid = false;         // captured with the current camera
     hipEvent_t dn_ev[PT_DENOISE_MAX_LEVELS + 3] = {};   // pt_debug_denoise_timing: capture 0-1, levels 2..
     float dn_capture_ms = 0.f, dn_ms = 0.f, dn_level_ms[PT_DENOISE_MAX_LEVELS] = {};
+    // temporal stage (pt/pt_denoise_temporal.h), allocated by the first pt_denoise_temporal
+    float4* d_tp[4] = {};            // base colour | N_base, base moments, integrated colour | N, moments | variance
+    bool tp_history = false;         // the integrated planes hold a history (of set tp_hist_set, camera tp_cam)
+    bool tp_base_valid = false;      // the base planes belong to the current capture
+    bool tp_result = false;          // a call has filled the planes (pt_temporal_get)
+    int tp_hist_set = 0;
+    int tp_demod = 0;                // demodulate_albedo of the history
+    CamDev tp_cam{};
+    hipEvent_t tp_ev[4] = {};        // pt_debug_denoise_timing: reprojection, integration, levels
+    float tp_ms[3] = {};
 };
 State g_primary;                 // the process's context (shard 0 of a multi-device context)
 State* gp = &g_primary;          // the context the host runtime works on now (see ShardScope)

@@ -4,6 +4,7 @@
 
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_denoise_temporal.h"
 #include "pt/pt_naive_mesh.h"
 
 namespace {
@@ -57,4 +58,16 @@ void pathtraceDenoise(float* out) {
     check(pt_set_camera(&hst_scene->state.camera), "pathtraceDenoise camera");
     check(pt_gbuffer_capture(1), "pathtraceDenoise feature buffer");
     check(pt_denoise(nullptr, last_iteration, nullptr, out), "pathtraceDenoise");
+}
+
+void pathtraceDenoiseTemporal(float* out) {
+    if (!hst_scene || last_iteration < 1) check(PT_E_STATE, "pathtraceDenoiseTemporal before pathtrace");
+    check(pt_set_camera(&hst_scene->state.camera), "pathtraceDenoiseTemporal camera");
+    // the feature buffer is captured when there is none for this camera; the history survives it
+    int rc = pt_denoise_temporal(nullptr, nullptr, last_iteration, nullptr, out);
+    if (rc == PT_E_STATE) {
+        check(pt_gbuffer_capture(1), "pathtraceDenoiseTemporal feature buffer");
+        rc = pt_denoise_temporal(nullptr, nullptr, last_iteration, nullptr, out);
+    }
+    check(rc, "pathtraceDenoiseTemporal");
 }

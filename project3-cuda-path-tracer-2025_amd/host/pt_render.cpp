@@ -8,13 +8,19 @@
 //             [--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh]
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
-//             [--denoise [LEVELS]] [--naive-mesh]
+//             [--denoise [LEVELS]] [--denoise-temporal [LEVELS]] [--naive-mesh]
 //
 // --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
 // triangle in array order, no BVH.  It implies --pipeline staged.
 // --denoise writes PREFIX.denoised.png beside the ordinary output: the averaged image through the
 // edge-avoiding a-trous filter of include/pt/pt_denoise.h (LEVELS passes, 1..8, default 5), saved
 // like saveImage with one sample.  The ordinary files are the same with or without it.
+// --denoise-temporal (with --events only: a single still camera has no history to use) writes a
+// .denoised.png beside every snapshot the session saves (S, ESC, reaching ITERATIONS), produced
+// through pt_denoise_temporal of include/pt/pt_denoise_temporal.h.  The feature buffer is captured
+// whenever the replayed viewer restarted accumulation.  The viewer restarts through pt_free /
+// pt_init, which drops the history: within a session the snapshots of one camera share their base,
+// and the filter is guided by the variance estimate.
 // --events replays a recorded window session through the viewer state machine of
 // include/pt/pt_viewer.h (main.cpp's GLFW callbacks + runCuda) instead of rendering --spp frames.
 // One event per line ('#' starts a comment):
@@ -30,6 +36,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -37,14 +44,43 @@
 #include "image_io.h"
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_denoise_temporal.h"
 #include "pt/pt_viewer.h"
 
+// --denoise-temporal: the .denoised.png beside the snapshot saveImage writes for `samples` frames
+// ("<img_dir>/<imageName>.<time_tag>.<samples>samp", pt_viewer_save_image)
+static int save_temporal(const std::string& img_dir, const std::string& image_name, const std::string& time_tag,
+                         int samples, int levels, int w, int h) {
+    pt_denoise_params dp;
+    pt_denoise_default_params(&dp);
+    dp.levels = levels;
+    std::vector<pt_vec3> den((size_t)w * h);
+    if (pt_denoise_temporal(&dp, nullptr, samples, nullptr, &den[0].x) != PT_OK) {
+        std::fprintf(stderr, "--denoise-temporal: %s\n", pt_last_error());
+        return PT_E_STATE;
+    }
+    std::ostringstream ss;
+    ss << img_dir << "/" << image_name << "." << time_tag << "." << (float)samples << "samp.denoised.png";
+    if (!ptio::write_png(ss.str(), ptio::to_rgb8(den, w, h, 1.0f), w, h)) return PT_E_INVALID;
+    std::printf("Saved %s (%d levels, temporal)\n", ss.str().c_str(), levels);
+    return PT_OK;
+}
+
 static int run_events(const std::string& scene_file, const pt_options& opts, int resx, int resy, int depth,
-                      const std::string& events, const std::string& img_dir, const std::string& time_tag) {
+                      const std::string& events, const std::string& img_dir, std::string time_tag, int temporal_levels) {
     pt_scene_file* sf = nullptr;
     if (pt_scene_load(scene_file.c_str(), resx, resy, depth, 0, &sf) != PT_OK) {
         std::fprintf(stderr, "%s\n", pt_scene_last_error());
         return 1;
+    }
+    int32_t scene_iterations = 0, scene_depth = 0;
+    char image_name[256] = "";
+    pt_scene_get_info(sf, &scene_iterations, &scene_depth, image_name, sizeof image_name);
+    if (temporal_levels > 0 && time_tag.empty()) {   // the snapshots' names are needed here: currentTimeString()
+        char buf[64];
+        const std::time_t now = std::time(nullptr);
+        std::strftime(buf, sizeof buf, "%Y-%m-%d_%H-%M-%Sz", std::gmtime(&now));
+        time_tag = buf;
     }
     pt_viewer* v = nullptr;
     if (pt_viewer_create(sf, &opts, img_dir.c_str(), time_tag.empty() ? nullptr : time_tag.c_str(), &v) != PT_OK) {
@@ -59,6 +95,14 @@ static int run_events(const std::string& scene_file, const pt_options& opts, int
     }
     std::string line;
     int rc = PT_OK, exited = 0, lineno = 0, frames = 0;
+    // the snapshot an event is about to save, through the temporal stage first (the tracer is freed at ITERATIONS)
+    auto temporal_snapshot = [&]() {
+        pt_viewer_state st;
+        pt_viewer_get_state(v, &st);
+        if (temporal_levels <= 0 || st.iteration < 1) return (int)PT_OK;
+        return save_temporal(img_dir, image_name, time_tag, st.iteration, temporal_levels, st.camera.resolution.x,
+                             st.camera.resolution.y);
+    };
     auto t0 = std::chrono::steady_clock::now();
     while (rc == PT_OK && !exited && std::getline(in, line)) {
         ++lineno;
@@ -78,14 +122,25 @@ static int run_events(const std::string& scene_file, const pt_options& opts, int
         } else if (cmd == "key") {
             int k = 0;
             ls >> k;
-            rc = pt_viewer_key(v, k, 0, PT_GLFW_PRESS, 0);
+            if (k == PT_GLFW_KEY_S || k == PT_GLFW_KEY_ESCAPE) rc = temporal_snapshot();
+            if (rc == PT_OK) rc = pt_viewer_key(v, k, 0, PT_GLFW_PRESS, 0);
             pt_viewer_state st;
             pt_viewer_get_state(v, &st);
             if (st.should_close) break;
         } else if (cmd == "frame") {
             int n = 1;
             ls >> n;
-            for (int i = 0; i < n && rc == PT_OK && !exited; ++i, ++frames) rc = pt_viewer_run_frame(v, &exited);
+            for (int i = 0; i < n && rc == PT_OK && !exited; ++i, ++frames) {
+                pt_viewer_state st;
+                pt_viewer_get_state(v, &st);
+                const bool restart = st.camchanged || st.iteration == 0;   // runCuda will restart accumulation
+                if (!restart && st.iteration >= scene_iterations) rc = temporal_snapshot();   // ... or save and exit
+                if (rc == PT_OK) rc = pt_viewer_run_frame(v, &exited);
+                if (rc == PT_OK && temporal_levels > 0 && restart && !exited && pt_gbuffer_capture(1) != PT_OK) {
+                    std::fprintf(stderr, "--denoise-temporal: %s\n", pt_last_error());
+                    rc = PT_E_STATE;
+                }
+            }
         } else if (cmd == "display") {
             std::string f;
             ls >> f;
@@ -118,13 +173,15 @@ int main(int argc, char** argv) {
         std::printf("Usage: %s SCENEFILE.json [--spp N] [--res WxH] [--depth D] [--out PREFIX] "
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
-                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]] [--naive-mesh]\n", argv[0]);
+                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]] "
+                    "[--denoise-temporal [LEVELS]] [--naive-mesh]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
     bool gpu_bvh = false, naive_mesh = false;
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
+    int temporal_levels = 0;  // 0: no --denoise-temporal
     pt_options opts;
     pt_default_options(&opts);
     for (int i = 2; i < argc; ++i) {
@@ -168,20 +225,21 @@ int main(int argc, char** argv) {
         else if (a == "--events") events = next();
         else if (a == "--img-dir") img_dir = next();
         else if (a == "--time-tag") time_tag = next();
-        else if (a == "--denoise") {   // the level count is optional: the next argument unless it is an option
+        else if (a == "--denoise" || a == "--denoise-temporal") {   // the level count is optional: the next argument unless it is an option
             pt_denoise_params dp;
             pt_denoise_default_params(&dp);
-            denoise_levels = dp.levels;
+            int& levels = a == "--denoise" ? denoise_levels : temporal_levels;
+            levels = dp.levels;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
                 const char* v = argv[++i];
                 char* end = nullptr;
                 const long n = std::strtol(v, &end, 10);
                 if (end == v || *end != '\0' || n < 1 || n > PT_DENOISE_MAX_LEVELS) {
-                    std::fprintf(stderr, "usage: --denoise [LEVELS], LEVELS an integer 1..%d, got '%s'\n",
+                    std::fprintf(stderr, "usage: %s [LEVELS], LEVELS an integer 1..%d, got '%s'\n", a.c_str(),
                                  PT_DENOISE_MAX_LEVELS, v);
                     return 2;
                 }
-                denoise_levels = (int)n;
+                levels = (int)n;
             }
         }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -190,7 +248,11 @@ int main(int argc, char** argv) {
         pathtraceSetNaiveMesh(true);
         opts.pipeline = PT_PIPELINE_STAGED;
     }
-    if (!events.empty()) return run_events(scene_file, opts, resx, resy, depth, events, img_dir, time_tag);
+    if (temporal_levels > 0 && events.empty()) {
+        std::fprintf(stderr, "--denoise-temporal needs --events FILE: a single still camera has no history to use\n");
+        return 2;
+    }
+    if (!events.empty()) return run_events(scene_file, opts, resx, resy, depth, events, img_dir, time_tag, temporal_levels);
     Scene* scene = nullptr;
     try {
         scene = new Scene(scene_file, resx, resy, depth, gpu_bvh);

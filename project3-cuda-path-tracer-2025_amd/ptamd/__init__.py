@@ -112,6 +112,11 @@ DENOISE_SYMBOLS = [
     "pt_denoise_default_params", "pt_gbuffer_capture", "pt_gbuffer_get", "pt_denoise", "pt_debug_denoise_timing",
     "pt_debug_denoise_times",
 ]
+# include/pt/pt_denoise_temporal.h (reprojected history + variance guidance in front of the filter)
+TEMPORAL_SYMBOLS = [
+    "pt_temporal_default_params", "pt_temporal_reset", "pt_denoise_temporal", "pt_temporal_get",
+    "pt_debug_temporal_times",
+]
 # include/pt/pt_naive_mesh.h (the reference's NAIVE_MESH_LOADING mode)
 NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_mesh_tile"]
 
@@ -156,6 +161,9 @@ def _load():
         "pt_denoise_default_params": (None, [vp]), "pt_gbuffer_capture": (i32, [i32]),
         "pt_gbuffer_get": (i32, [vp, vp, vp, i64]), "pt_denoise": (i32, [vp, i32, vp, vp]),
         "pt_debug_denoise_timing": (i32, [i32]), "pt_debug_denoise_times": (i32, [vp, vp, vp]),
+        "pt_temporal_default_params": (None, [vp]), "pt_temporal_reset": (i32, []),
+        "pt_denoise_temporal": (i32, [vp, vp, i32, vp, vp]), "pt_temporal_get": (i32, [vp, vp, vp, vp, i64]),
+        "pt_debug_temporal_times": (i32, [vp, vp, vp]),
         "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
     }
     for name, (res, args) in sig.items():
@@ -244,6 +252,23 @@ def denoise_default_params(**kw) -> _DenoiseParams:
             raise TypeError(f"unknown denoise parameter {k}")
         setattr(p, k, v)
     return p
+
+
+class _TemporalParams(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_int32), ("normal_cos_min", ctypes.c_float), ("plane_tol", ctypes.c_float),
+                ("variance_history_min", ctypes.c_int32), ("sigma_variance", ctypes.c_float)]
+
+
+def temporal_default_params(**kw) -> _TemporalParams:
+    """pt_temporal_params with overrides (max_history, normal_cos_min, plane_tol,
+    variance_history_min, sigma_variance)."""
+    t = _TemporalParams()
+    lib.pt_temporal_default_params(ctypes.byref(t))
+    for k, v in kw.items():
+        if k not in dict(_TemporalParams._fields_):
+            raise TypeError(f"unknown temporal parameter {k}")
+        setattr(t, k, v)
+    return t
 
 
 class _TextureC(ctypes.Structure):
@@ -485,6 +510,33 @@ class PathTracer:
         p = denoise_default_params(**params)
         out = np.empty((self.height, self.width, 3), np.float32)
         _check(lib.pt_denoise(ctypes.byref(p), int(samples), pbo_device_ptr, out.ctypes.data), "pt_denoise")
+        return out
+
+    # ---- temporal stage (include/pt/pt_denoise_temporal.h) ----
+    temporal_default_params = staticmethod(temporal_default_params)
+
+    def denoise_temporal(self, samples: int, pbo_device_ptr: int | None = None, temporal=None, **params) -> np.ndarray:
+        """denoise() with the temporal stage in front: the history of the earlier calls reprojected
+        into the captured feature buffer's pixels, integrated with the accumulated image / samples,
+        and filtered under variance guidance: (h, w, 3) float32.  `temporal`: a dict of
+        pt_temporal_params overrides or a temporal_default_params() result."""
+        p = denoise_default_params(**params)
+        t = temporal if isinstance(temporal, _TemporalParams) else temporal_default_params(**(temporal or {}))
+        out = np.empty((self.height, self.width, 3), np.float32)
+        _check(lib.pt_denoise_temporal(ctypes.byref(p), ctypes.byref(t), int(samples), pbo_device_ptr, out.ctypes.data),
+               "pt_denoise_temporal")
+        return out
+
+    def temporal_reset(self):
+        """Drop all history."""
+        _check(lib.pt_temporal_reset(), "pt_temporal_reset")
+
+    def temporal_planes(self) -> dict:
+        """The last denoise_temporal call's planes: {"base_color", "base_moments", "color", "moments"},
+        each (h, w, 4) float32 (see pt_temporal_get)."""
+        out = {k: np.empty((self.height, self.width, 4), np.float32)
+               for k in ("base_color", "base_moments", "color", "moments")}
+        _check(lib.pt_temporal_get(*(out[k].ctypes.data for k in out), self.pixels), "pt_temporal_get")
         return out
 
     # ---- single-kernel entry points (tests) ----

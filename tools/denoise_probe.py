@@ -1,12 +1,19 @@
 """Time of the denoiser's kernels (include/pt/pt_denoise.h) on cornell at 800^2 and 1600^2.
 
     python tools/denoise_probe.py [out.json]        (default profiles/denoise_probe.json)
+    python tools/denoise_probe.py --temporal [out.json]   (default profiles/denoise_temporal_probe.json)
 
 8 spp are accumulated, then 5 warm-up and 20 timed calls each of pt_gbuffer_capture and of
 pt_denoise without the host copy (default parameters: 5 levels), timed by HIP events on the
 library's stream (pt_debug_denoise_timing).  Per level the record holds the median time, the
 unique bytes of the traffic model (16 B colour read + 32 B guides read + 16 B
 written per pixel) and the fraction of 8 TB/s that makes.
+
+--temporal: the temporal stage (include/pt/pt_denoise_temporal.h) at 800^2, 5 levels.  Every
+iteration moves the camera (two cameras in turn), captures, and runs pt_denoise_temporal (which
+reprojects, the capture being new) and pt_denoise on the same image, interleaved in one process;
+the record holds the medians of reprojection, integration + variance and the levels, and
+pt_denoise's time beside them.
 """
 import ctypes
 import json
@@ -57,10 +64,43 @@ def probe(res):
     }
 
 
+def probe_temporal(res):
+    sc = ptamd.SceneFile(os.path.join(REPO, "scenes", "cornell.json"), res=(res, res))
+    tr = ptamd.PathTracer(sc)
+    L = ptamd.lib
+    tr.trace_frames(1, SPP)
+    tr.synchronize()
+    cams = [sc.camera.copy(), sc.camera.copy()]
+    cams[1]["position"][0][0] += 0.25
+    p = ptamd.denoise_default_params()
+    assert L.pt_debug_denoise_timing(1) == 0
+    rows = []
+    r, i, lv, d = (ctypes.c_float() for _ in range(4))
+    for k in range(WARMUP + CALLS):
+        assert L.pt_set_camera(cams[k & 1].ctypes.data) == 0
+        assert L.pt_gbuffer_capture(1) == 0, L.pt_last_error()
+        assert L.pt_denoise_temporal(ctypes.byref(p), None, SPP, None, None) == 0, L.pt_last_error()
+        assert L.pt_debug_temporal_times(ctypes.byref(r), ctypes.byref(i), ctypes.byref(lv)) == 0
+        assert L.pt_denoise(ctypes.byref(p), SPP, None, None) == 0, L.pt_last_error()
+        assert L.pt_debug_denoise_times(None, ctypes.byref(d), None) == 0
+        if k >= WARMUP:
+            rows.append((r.value, i.value, lv.value, d.value))
+    L.pt_debug_denoise_timing(0)
+    tr.free()
+    med = [statistics.median(c) for c in zip(*rows)]
+    return {"scene": "cornell", "res": [res, res], "spp": SPP, "levels": p.levels, "warmup": WARMUP, "calls": CALLS,
+            "reproject_ms": med[0], "integrate_variance_ms": med[1], "levels_ms": med[2],
+            "temporal_total_ms": med[0] + med[1] + med[2], "pt_denoise_ms": med[3],
+            "min_max": [[min(c), max(c)] for c in zip(*rows)]}
+
+
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "profiles", "denoise_probe.json")
-    rec = {"tool": "tools/denoise_probe.py", "timer": "HIP events on the context's stream, no host copy",
-           "runs": [probe(800), probe(1600)]}
+    args = [a for a in sys.argv[1:] if a != "--temporal"]
+    temporal = len(args) != len(sys.argv) - 1
+    out = args[0] if args else os.path.join(REPO, "profiles", "denoise_temporal_probe.json" if temporal else "denoise_probe.json")
+    rec = {"tool": "tools/denoise_probe.py" + (" --temporal" if temporal else ""),
+           "timer": "HIP events on the context's stream, no host copy",
+           "runs": [probe_temporal(800)] if temporal else [probe(800), probe(1600)]}
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
