@@ -49,6 +49,9 @@
  * The integrated planes, not the filtered output, become the history.
  *
  * One unsharded device context only, and not in naive mesh mode (PT_E_UNSUPPORTED), as pt_denoise.
+ * PT_E_UNSUPPORTED as well after a through-capture with max_specular > 0
+ * (include/pt/pt_gbuffer_through.h): the reprojection projects the recorded position through the
+ * pinhole camera, which is wrong for a surface seen in a mirror or through glass.
  * Memory: one more set of three feature planes and four float4 planes (base and integrated colour
  * and moments; the history lives in the integrated planes until the next capture's reprojection
  * has read it), allocated at the first call and freed by pt_free.

@@ -24,17 +24,13 @@ struct GBuf {
     float4* alb;   // albedo.rgb | materialId as float    (0, -1 on a miss)
 };
 
-template <bool HAS_BVH, bool BVH_FAST>
-__global__ __launch_bounds__(BLOCK) void k_gbuffer(SceneDev sc, GBuf g, int iter, int n) {
-    extern __shared__ int s_stack[];
-    const int gid = blockIdx.x * BLOCK + threadIdx.x;
-    if (gid >= n) return;
-    const PathReg p = camera_ray(sc.cam, iter, sc.trace_depth, gid);
-    const Hit h = intersect_scene<HAS_BVH, BVH_FAST>(sc, p.o, p.d, s_stack + threadIdx.x);
+// the three planes of pixel `pix` from the hit h of the ray (o, d); t: what the t slot holds on a hit
+// (k_gbuffer: h.t; the chains of pt_gbuffer_through_kernels.h: the sum over their segments)
+PT_DEV void gbuffer_write(const SceneDev& sc, const GBuf& g, int pix, f3 o, f3 d, const Hit& h, float t) {
     float4 pos = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 alb = make_float4(0.f, 0.f, 0.f, -1.0f);
     if (h.t > 0.0f) {
-        const f3 x = p.o + p.d * h.t;   // the shading point, rounded as shade_path rounds it
+        const f3 x = o + d * h.t;   // the shading point, rounded as shade_path rounds it
         pos = make_float4(x.x, x.y, x.z, 1.0f);
         const DevMaterial m = sc.mats[h.mat];
         f3 c = mk(m.color[0], m.color[1], m.color[2]);
@@ -50,9 +46,19 @@ __global__ __launch_bounds__(BLOCK) void k_gbuffer(SceneDev sc, GBuf g, int iter
         }
         alb = make_float4(c.x, c.y, c.z, (float)h.mat);
     }
-    g.nt[gid] = make_float4(h.n.x, h.n.y, h.n.z, h.t);
-    g.pos[gid] = pos;
-    g.alb[gid] = alb;
+    g.nt[pix] = make_float4(h.n.x, h.n.y, h.n.z, h.t > 0.0f ? t : h.t);
+    g.pos[pix] = pos;
+    g.alb[pix] = alb;
+}
+
+template <bool HAS_BVH, bool BVH_FAST>
+__global__ __launch_bounds__(BLOCK) void k_gbuffer(SceneDev sc, GBuf g, int iter, int n) {
+    extern __shared__ int s_stack[];
+    const int gid = blockIdx.x * BLOCK + threadIdx.x;
+    if (gid >= n) return;
+    const PathReg p = camera_ray(sc.cam, iter, sc.trace_depth, gid);
+    const Hit h = intersect_scene<HAS_BVH, BVH_FAST>(sc, p.o, p.d, s_stack + threadIdx.x);
+    gbuffer_write(sc, g, gid, p.o, p.d, h, h.t);
 }
 
 // ---- the filter ----------------------------------------------------------------------------

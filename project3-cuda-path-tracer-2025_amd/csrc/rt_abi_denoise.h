@@ -28,12 +28,16 @@ void pt_denoise_default_params(pt_denoise_params* p) {
     p->demodulate_albedo = 1;
 }
 
-int32_t pt_gbuffer_capture(int32_t iteration) {
-    RC(denoise_ctx("pt_gbuffer_capture"));
-    if (gp->naive) return fail(PT_E_UNSUPPORTED, "pt_gbuffer_capture: not available in naive mesh mode");
+// the start of a capture (this file's and rt_abi_gbuffer_through.h's): the context and iteration
+// checks, the planes allocated, the captured buffer invalid until the capture completes; g: the
+// plane set to write
+static int32_t capture_begin(const char* what, int32_t iteration, GBuf* g) {
+    RC(denoise_ctx(what));
+    if (gp->naive) return fail(PT_E_UNSUPPORTED, "%s: not available in naive mesh mode", what);
     if (iteration <= 0) return fail(PT_E_INVALID, "iteration is 1-based, got %d", iteration);
     const int n = gp->pixels_total;
     gp->gbuf_valid = false;
+    gp->gbuf_through = -1;
     if (!gp->d_gbuf[0][0]) {
         for (float4*& p : gp->d_gbuf[0]) RC(dalloc(&p, (size_t)n));
         for (float4*& p : gp->d_dn_color) RC(dalloc(&p, (size_t)n));
@@ -42,7 +46,14 @@ int32_t pt_gbuffer_capture(int32_t iteration) {
     if (gp->tp_history && gp->tp_hist_set == gp->gbuf_cur) gp->gbuf_cur ^= 1;
     gp->tp_base_valid = false;
     float4* const* cur = gp->d_gbuf[gp->gbuf_cur];
-    const GBuf g{cur[0], cur[1], cur[2]};
+    *g = GBuf{cur[0], cur[1], cur[2]};
+    return PT_OK;
+}
+
+int32_t pt_gbuffer_capture(int32_t iteration) {
+    GBuf g;
+    RC(capture_begin("pt_gbuffer_capture", iteration, &g));
+    const int n = gp->pixels_total;
     if (g_dn_timing) RC(denoise_event(0));
     // the traversal pt_test_intersect (and the staged pipeline) runs for this context's options
     if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))

@@ -53,6 +53,10 @@ int32_t pt_denoise_temporal(const pt_denoise_params* params, const pt_temporal_p
         return fail(PT_E_INVALID, "pt_denoise_temporal: variance_history_min must be >= 0, got %d", t.variance_history_min);
     if (!gp->gbuf_valid)
         return fail(PT_E_STATE, "pt_denoise_temporal: no feature buffer captured for this camera (pt_gbuffer_capture)");
+    if (gp->gbuf_through > 0)
+        return fail(PT_E_UNSUPPORTED, "pt_denoise_temporal: the feature buffer is a through-capture (max_specular %d): "
+                    "a position behind a reflection or refraction cannot be reprojected through the pinhole camera",
+                    gp->gbuf_through);
     const int n = gp->pixels_total;
     if (!gp->d_tp[0]) {
         for (float4*& q : gp->d_gbuf[1]) RC(dalloc(&q, (size_t)n));

@@ -177,6 +177,9 @@ void free_all() {
         for (float4*& p : set) dfree(p);
     for (float4*& p : gp->d_dn_color) dfree(p);
     for (float4*& p : gp->d_tp) dfree(p);
+    for (float4*& p : gp->d_chain_q) dfree(p);
+    dfree(gp->d_chain_followed);
+    dfree(gp->d_chain_cnt);
     for (hipEvent_t& e : gp->dn_ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     for (hipEvent_t& e : gp->tp_ev)

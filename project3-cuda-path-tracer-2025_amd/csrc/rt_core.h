@@ -148,6 +148,11 @@ struct State {
     bool gbuf_valid = false;         // captured with the current camera
     hipEvent_t dn_ev[PT_DENOISE_MAX_LEVELS + 3] = {};   // pt_debug_denoise_timing: capture 0-1, levels 2..
     float dn_capture_ms = 0.f, dn_ms = 0.f, dn_level_ms[PT_DENOISE_MAX_LEVELS] = {};
+    // through-capture (pt/pt_gbuffer_through.h), allocated by the first pt_gbuffer_capture_through
+    int gbuf_through = -1;           // max_specular of the captured buffer; -1: pt_gbuffer_capture's
+    float4* d_chain_q[2] = {nullptr, nullptr};   // ping-pong ray queues: pixels x (origin | pixel), then x (direction | t_sum)
+    int* d_chain_followed = nullptr; // delta surfaces followed, per pixel
+    int* d_chain_cnt = nullptr;      // a queue counter per round, CNT_PAD ints apart
     // temporal stage (pt/pt_denoise_temporal.h), allocated by the first pt_denoise_temporal
     float4* d_tp[4] = {};            // base colour | N_base, base moments, integrated colour | N, moments | variance
     bool tp_history = false;         // the integrated planes hold a history (of set tp_hist_set, camera tp_cam)

@@ -8,13 +8,15 @@
 //             [--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh]
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
-//             [--denoise [LEVELS]] [--denoise-temporal [LEVELS]] [--naive-mesh]
+//             [--denoise [LEVELS] [--denoise-through K]] [--denoise-temporal [LEVELS]] [--naive-mesh]
 //
 // --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
 // triangle in array order, no BVH.  It implies --pipeline staged.
 // --denoise writes PREFIX.denoised.png beside the ordinary output: the averaged image through the
 // edge-avoiding a-trous filter of include/pt/pt_denoise.h (LEVELS passes, 1..8, default 5), saved
 // like saveImage with one sample.  The ordinary files are the same with or without it.
+// --denoise-through K (with --denoise) guides the filter by the first non-specular surface behind up
+// to K mirror / glass surfaces (include/pt/pt_gbuffer_through.h, K = 0..8) instead of the first hit.
 // --denoise-temporal (with --events only: a single still camera has no history to use) writes a
 // .denoised.png beside every snapshot the session saves (S, ESC, reaching ITERATIONS), produced
 // through pt_denoise_temporal of include/pt/pt_denoise_temporal.h.  The feature buffer is captured
@@ -45,6 +47,7 @@
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
 #include "pt/pt_denoise_temporal.h"
+#include "pt/pt_gbuffer_through.h"
 #include "pt/pt_viewer.h"
 
 // --denoise-temporal: the .denoised.png beside the snapshot saveImage writes for `samples` frames
@@ -173,7 +176,7 @@ int main(int argc, char** argv) {
         std::printf("Usage: %s SCENEFILE.json [--spp N] [--res WxH] [--depth D] [--out PREFIX] "
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
-                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS]] "
+                    "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS] [--denoise-through K]] "
                     "[--denoise-temporal [LEVELS]] [--naive-mesh]\n", argv[0]);
         return 1;
     }
@@ -182,6 +185,7 @@ int main(int argc, char** argv) {
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
     int temporal_levels = 0;  // 0: no --denoise-temporal
+    int denoise_through = 0;  // --denoise-through K: specular surfaces the guides look through
     pt_options opts;
     pt_default_options(&opts);
     for (int i = 2; i < argc; ++i) {
@@ -242,6 +246,16 @@ int main(int argc, char** argv) {
                 levels = (int)n;
             }
         }
+        else if (a == "--denoise-through") {
+            const char* v = next();
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 0 || n > PT_GBUFFER_THROUGH_MAX) {
+                std::fprintf(stderr, "usage: --denoise-through K, K an integer 0..%d, got '%s'\n", PT_GBUFFER_THROUGH_MAX, v);
+                return 2;
+            }
+            denoise_through = (int)n;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (naive_mesh) {   // the mode runs on the staged pipeline
@@ -250,6 +264,10 @@ int main(int argc, char** argv) {
     }
     if (temporal_levels > 0 && events.empty()) {
         std::fprintf(stderr, "--denoise-temporal needs --events FILE: a single still camera has no history to use\n");
+        return 2;
+    }
+    if (denoise_through > 0 && denoise_levels == 0) {
+        std::fprintf(stderr, "--denoise-through needs --denoise: it chooses the guides of that filter\n");
         return 2;
     }
     if (!events.empty()) return run_events(scene_file, opts, resx, resy, depth, events, img_dir, time_tag, temporal_levels);
@@ -284,12 +302,16 @@ int main(int argc, char** argv) {
         pt_denoise_default_params(&dp);
         dp.levels = denoise_levels;
         std::vector<pt_vec3> den((size_t)width * height);
-        if (pt_gbuffer_capture(1) != PT_OK || pt_denoise(&dp, iterations, nullptr, &den[0].x) != PT_OK) {
+        const int32_t captured = denoise_through > 0 ? pt_gbuffer_capture_through(1, denoise_through) : pt_gbuffer_capture(1);
+        if (captured != PT_OK || pt_denoise(&dp, iterations, nullptr, &den[0].x) != PT_OK) {
             std::fprintf(stderr, "--denoise: %s\n", pt_last_error());
             ok = false;
         } else {
             ok = ptio::write_png(out + ".denoised.png", ptio::to_rgb8(den, width, height, 1.0f), width, height);
-            std::printf("Saved %s.denoised.png (%d levels)\n", out.c_str(), denoise_levels);
+            if (denoise_through > 0)
+                std::printf("Saved %s.denoised.png (%d levels, guides through %d specular surfaces)\n", out.c_str(),
+                            denoise_levels, denoise_through);
+            else std::printf("Saved %s.denoised.png (%d levels)\n", out.c_str(), denoise_levels);
         }
     }
     pathtraceFree();

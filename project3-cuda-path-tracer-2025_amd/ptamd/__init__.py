@@ -117,6 +117,8 @@ TEMPORAL_SYMBOLS = [
     "pt_temporal_default_params", "pt_temporal_reset", "pt_denoise_temporal", "pt_temporal_get",
     "pt_debug_temporal_times",
 ]
+# include/pt/pt_gbuffer_through.h (feature planes of the first non-specular hit)
+GBUFFER_THROUGH_SYMBOLS = ["pt_gbuffer_capture_through", "pt_gbuffer_get_chain"]
 # include/pt/pt_naive_mesh.h (the reference's NAIVE_MESH_LOADING mode)
 NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_mesh_tile"]
 
@@ -164,6 +166,7 @@ def _load():
         "pt_temporal_default_params": (None, [vp]), "pt_temporal_reset": (i32, []),
         "pt_denoise_temporal": (i32, [vp, vp, i32, vp, vp]), "pt_temporal_get": (i32, [vp, vp, vp, vp, i64]),
         "pt_debug_temporal_times": (i32, [vp, vp, vp]),
+        "pt_gbuffer_capture_through": (i32, [i32, i32]), "pt_gbuffer_get_chain": (i32, [vp, i64]),
         "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
     }
     for name, (res, args) in sig.items():
@@ -495,13 +498,21 @@ class PathTracer:
         return out
 
     # ---- denoiser (include/pt/pt_denoise.h) ----
-    def capture_gbuffer(self, iteration: int = 1) -> dict:
+    def capture_gbuffer(self, iteration: int = 1, through: int = 0) -> dict:
         """First hit of generateRayFromCamera(iteration) per pixel: {"normal_t", "position",
-        "albedo_mat"}, each (h, w, 4) float32 (see pt_gbuffer_get)."""
-        _check(lib.pt_gbuffer_capture(int(iteration)), "pt_gbuffer_capture")
+        "albedo_mat"}, each (h, w, 4) float32 (see pt_gbuffer_get).  through = K > 0: the first
+        non-specular hit behind up to K mirror / glass surfaces (include/pt/pt_gbuffer_through.h),
+        and "followed", (h, w) int32: the specular surfaces each pixel's ray followed."""
+        if through:
+            _check(lib.pt_gbuffer_capture_through(int(iteration), int(through)), "pt_gbuffer_capture_through")
+        else:
+            _check(lib.pt_gbuffer_capture(int(iteration)), "pt_gbuffer_capture")
         out = {k: np.empty((self.height, self.width, 4), np.float32) for k in ("normal_t", "position", "albedo_mat")}
         _check(lib.pt_gbuffer_get(out["normal_t"].ctypes.data, out["position"].ctypes.data,
                                   out["albedo_mat"].ctypes.data, self.pixels), "pt_gbuffer_get")
+        if through:
+            out["followed"] = np.empty((self.height, self.width), np.int32)
+            _check(lib.pt_gbuffer_get_chain(out["followed"].ctypes.data, self.pixels), "pt_gbuffer_get_chain")
         return out
 
     def denoise(self, samples: int, pbo_device_ptr: int | None = None, **params) -> np.ndarray:

@@ -2,6 +2,7 @@
 
     python tools/denoise_probe.py [out.json]        (default profiles/denoise_probe.json)
     python tools/denoise_probe.py --temporal [out.json]   (default profiles/denoise_temporal_probe.json)
+    python tools/denoise_probe.py --through [out.json]    (default profiles/gbuffer_through_probe.json)
 
 8 spp are accumulated, then 5 warm-up and 20 timed calls each of pt_gbuffer_capture and of
 pt_denoise without the host copy (default parameters: 5 levels), timed by HIP events on the
@@ -14,6 +15,11 @@ iteration moves the camera (two cameras in turn), captures, and runs pt_denoise_
 reprojects, the capture being new) and pt_denoise on the same image, interleaved in one process;
 the record holds the medians of reprojection, integration + variance and the levels, and
 pt_denoise's time beside them.
+
+--through: the through-capture (include/pt/pt_gbuffer_through.h) at 800^2 on cornell (no delta
+surface) and cornell_glass_test: every iteration times pt_gbuffer_capture and
+pt_gbuffer_capture_through with K = 0 and K = 4 in turn, interleaved in one process; the record holds
+the medians, and the pixels that followed 1..4 delta surfaces.
 """
 import ctypes
 import json
@@ -94,13 +100,42 @@ def probe_temporal(res):
             "min_max": [[min(c), max(c)] for c in zip(*rows)]}
 
 
+def probe_through(scene, res):
+    sc = ptamd.SceneFile(os.path.join(REPO, "scenes", scene + ".json"), res=(res, res))
+    tr = ptamd.PathTracer(sc)
+    L = ptamd.lib
+    followed = tr.capture_gbuffer(1, through=4)["followed"]
+    assert L.pt_debug_denoise_timing(1) == 0
+    calls = {"pt_gbuffer_capture": lambda: L.pt_gbuffer_capture(1),
+             "through_K0": lambda: L.pt_gbuffer_capture_through(1, 0),
+             "through_K4": lambda: L.pt_gbuffer_capture_through(1, 4)}
+    rows = {k: [] for k in calls}
+    c = ctypes.c_float()
+    for k in range(WARMUP + CALLS):
+        for name, call in calls.items():
+            assert call() == 0, L.pt_last_error()
+            assert L.pt_debug_denoise_times(ctypes.byref(c), None, None) == 0
+            if k >= WARMUP:
+                rows[name].append(c.value)
+    L.pt_debug_denoise_timing(0)
+    tr.free()
+    return {"scene": scene, "res": [res, res], "warmup": WARMUP, "calls": CALLS,
+            "pixels_by_followed": [int((followed == k).sum()) for k in range(5)],
+            "capture_ms": {k: statistics.median(v) for k, v in rows.items()},
+            "capture_ms_min_max": {k: [min(v), max(v)] for k, v in rows.items()}}
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--temporal"]
-    temporal = len(args) != len(sys.argv) - 1
-    out = args[0] if args else os.path.join(REPO, "profiles", "denoise_temporal_probe.json" if temporal else "denoise_probe.json")
-    rec = {"tool": "tools/denoise_probe.py" + (" --temporal" if temporal else ""),
+    modes = {"--temporal": "denoise_temporal_probe.json", "--through": "gbuffer_through_probe.json"}
+    args = [a for a in sys.argv[1:] if a not in modes]
+    mode = next((a for a in sys.argv[1:] if a in modes), "")
+    out = args[0] if args else os.path.join(REPO, "profiles", modes.get(mode, "denoise_probe.json"))
+    runs = {"--temporal": lambda: [probe_temporal(800)],
+            "--through": lambda: [probe_through("cornell", 800), probe_through("cornell_glass_test", 800)],
+            "": lambda: [probe(800), probe(1600)]}[mode]()
+    rec = {"tool": ("tools/denoise_probe.py " + mode).strip(),
            "timer": "HIP events on the context's stream, no host copy",
-           "runs": [probe_temporal(800)] if temporal else [probe(800), probe(1600)]}
+           "runs": runs}
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
