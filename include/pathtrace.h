@@ -23,6 +23,11 @@ void pathtraceSetOptions(const pt_options& opts);
 // image itself is untouched.
 void pathtraceDenoise(float* out);
 
+// Framework addition: pathtraceDenoise with the blockwise feature regression of
+// pt/pt_denoise_regress.h in place of the a-trous filter (default parameters, feature buffer captured
+// at iteration 1) -> out[width * height * 3].  The accumulated image itself is untouched.
+void pathtraceDenoiseRegress(float* out);
+
 // Framework addition: pathtraceDenoise with the temporal stage of pt/pt_denoise_temporal.h in front
 // (default parameters): the history of the earlier calls is reprojected through camera changes and
 // a per-pixel variance guides the filter.  The feature buffer is captured when the camera changed

@@ -40,6 +40,7 @@
 
 #include "pt/pathtrace_abi.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
 #include "pt/pt_gbuffer_through.h"
 #include "pt/pt_naive_mesh.h"
@@ -47,6 +48,7 @@
 #include "pt_denoise_kernels.h"
 #include "pt_gbuffer_through_kernels.h"
 #include "pt_temporal_kernels.h"
+#include "pt_regress_kernels.h"
 #include "pt_naive_mesh_kernels.h"
 #include "scene_layout.h"
 #include "band_layout.h"
@@ -808,6 +810,7 @@ int32_t pt_reset_stats(void) {
 #include "rt_abi_denoise.h"
 #include "rt_abi_gbuffer_through.h"
 #include "rt_abi_temporal.h"
+#include "rt_abi_regress.h"
 #include "rt_abi_test.h"
 
 }  // extern "C"

@@ -163,6 +163,11 @@ struct State {
     CamDev tp_cam{};
     hipEvent_t tp_ev[4] = {};        // pt_debug_denoise_timing: reprojection, integration, levels
     float tp_ms[3] = {};
+    // feature regression (pt/pt_denoise_regress.h), allocated by the first pt_denoise_regress
+    float* d_rg_tab = nullptr;       // the block table, RG_REC floats per block
+    bool rg_result = false;          // a call has filled the table (pt_regress_get)
+    hipEvent_t rg_ev[3] = {};        // pt_debug_denoise_timing: fit, apply
+    float rg_ms[2] = {};
 };
 State g_primary;                 // the process's context (shard 0 of a multi-device context)
 State* gp = &g_primary;          // the context the host runtime works on now (see ShardScope)

@@ -4,6 +4,7 @@
 
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
 #include "pt/pt_naive_mesh.h"
 
@@ -58,6 +59,13 @@ void pathtraceDenoise(float* out) {
     check(pt_set_camera(&hst_scene->state.camera), "pathtraceDenoise camera");
     check(pt_gbuffer_capture(1), "pathtraceDenoise feature buffer");
     check(pt_denoise(nullptr, last_iteration, nullptr, out), "pathtraceDenoise");
+}
+
+void pathtraceDenoiseRegress(float* out) {
+    if (!hst_scene || last_iteration < 1) check(PT_E_STATE, "pathtraceDenoiseRegress before pathtrace");
+    check(pt_set_camera(&hst_scene->state.camera), "pathtraceDenoiseRegress camera");
+    check(pt_gbuffer_capture(1), "pathtraceDenoiseRegress feature buffer");
+    check(pt_denoise_regress(nullptr, last_iteration, nullptr, out), "pathtraceDenoiseRegress");
 }
 
 void pathtraceDenoiseTemporal(float* out) {

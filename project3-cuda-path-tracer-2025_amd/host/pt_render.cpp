@@ -9,6 +9,7 @@
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
 //             [--denoise [LEVELS] [--denoise-through K]] [--denoise-temporal [LEVELS]] [--naive-mesh]
+//             [--denoise-regress [RIDGE]]
 //
 // --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
 // triangle in array order, no BVH.  It implies --pipeline staged.
@@ -17,6 +18,9 @@
 // like saveImage with one sample.  The ordinary files are the same with or without it.
 // --denoise-through K (with --denoise) guides the filter by the first non-specular surface behind up
 // to K mirror / glass surfaces (include/pt/pt_gbuffer_through.h, K = 0..8) instead of the first hit.
+// --denoise-regress writes PREFIX.regressed.png beside the ordinary output: the averaged image through
+// the blockwise feature regression of include/pt/pt_denoise_regress.h (RIDGE > 0, default 1e-3), saved
+// like saveImage with one sample (guides: the first hits of iteration 1).
 // --denoise-temporal (with --events only: a single still camera has no history to use) writes a
 // .denoised.png beside every snapshot the session saves (S, ESC, reaching ITERATIONS), produced
 // through pt_denoise_temporal of include/pt/pt_denoise_temporal.h.  The feature buffer is captured
@@ -46,6 +50,7 @@
 #include "image_io.h"
 #include "pathtrace.h"
 #include "pt/pt_denoise.h"
+#include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
 #include "pt/pt_gbuffer_through.h"
 #include "pt/pt_viewer.h"
@@ -177,7 +182,7 @@ int main(int argc, char** argv) {
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
                     "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS] [--denoise-through K]] "
-                    "[--denoise-temporal [LEVELS]] [--naive-mesh]\n", argv[0]);
+                    "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
@@ -186,6 +191,7 @@ int main(int argc, char** argv) {
     int denoise_levels = 0;   // 0: no --denoise
     int temporal_levels = 0;  // 0: no --denoise-temporal
     int denoise_through = 0;  // --denoise-through K: specular surfaces the guides look through
+    float regress_ridge = 0.0f;   // 0: no --denoise-regress
     pt_options opts;
     pt_default_options(&opts);
     for (int i = 2; i < argc; ++i) {
@@ -244,6 +250,21 @@ int main(int argc, char** argv) {
                     return 2;
                 }
                 levels = (int)n;
+            }
+        }
+        else if (a == "--denoise-regress") {   // the ridge is optional, like the level count above
+            pt_regress_params rp;
+            pt_regress_default_params(&rp);
+            regress_ridge = rp.ridge;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* v = argv[++i];
+                char* end = nullptr;
+                const float r = std::strtof(v, &end);
+                if (end == v || *end != '\0' || !(r > 0.0f) || !(r <= 3.0e38f)) {
+                    std::fprintf(stderr, "usage: --denoise-regress [RIDGE], RIDGE a finite number > 0, got '%s'\n", v);
+                    return 2;
+                }
+                regress_ridge = r;
             }
         }
         else if (a == "--denoise-through") {
@@ -312,6 +333,19 @@ int main(int argc, char** argv) {
                 std::printf("Saved %s.denoised.png (%d levels, guides through %d specular surfaces)\n", out.c_str(),
                             denoise_levels, denoise_through);
             else std::printf("Saved %s.denoised.png (%d levels)\n", out.c_str(), denoise_levels);
+        }
+    }
+    if (regress_ridge > 0.0f && ok) {   // first hits of iteration 1, then the fit
+        pt_regress_params rp;
+        pt_regress_default_params(&rp);
+        rp.ridge = regress_ridge;
+        std::vector<pt_vec3> reg((size_t)width * height);
+        if (pt_gbuffer_capture(1) != PT_OK || pt_denoise_regress(&rp, iterations, nullptr, &reg[0].x) != PT_OK) {
+            std::fprintf(stderr, "--denoise-regress: %s\n", pt_last_error());
+            ok = false;
+        } else {
+            ok = ptio::write_png(out + ".regressed.png", ptio::to_rgb8(reg, width, height, 1.0f), width, height);
+            std::printf("Saved %s.regressed.png (ridge %g)\n", out.c_str(), (double)regress_ridge);
         }
     }
     pathtraceFree();

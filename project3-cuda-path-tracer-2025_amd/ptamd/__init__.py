@@ -117,6 +117,9 @@ TEMPORAL_SYMBOLS = [
     "pt_temporal_default_params", "pt_temporal_reset", "pt_denoise_temporal", "pt_temporal_get",
     "pt_debug_temporal_times",
 ]
+# include/pt/pt_denoise_regress.h (blockwise feature regression beside the a-trous filter)
+REGRESS_SYMBOLS = ["pt_regress_default_params", "pt_denoise_regress", "pt_regress_get", "pt_debug_regress_times"]
+REGRESS_BLOCK_FLOATS = 37   # n | lo.xyz | hi.xyz | beta[10][3]
 # include/pt/pt_gbuffer_through.h (feature planes of the first non-specular hit)
 GBUFFER_THROUGH_SYMBOLS = ["pt_gbuffer_capture_through", "pt_gbuffer_get_chain"]
 # include/pt/pt_naive_mesh.h (the reference's NAIVE_MESH_LOADING mode)
@@ -166,6 +169,8 @@ def _load():
         "pt_temporal_default_params": (None, [vp]), "pt_temporal_reset": (i32, []),
         "pt_denoise_temporal": (i32, [vp, vp, i32, vp, vp]), "pt_temporal_get": (i32, [vp, vp, vp, vp, i64]),
         "pt_debug_temporal_times": (i32, [vp, vp, vp]),
+        "pt_regress_default_params": (None, [vp]), "pt_denoise_regress": (i32, [vp, i32, vp, vp]),
+        "pt_regress_get": (i32, [vp, i64]), "pt_debug_regress_times": (i32, [vp, vp]),
         "pt_gbuffer_capture_through": (i32, [i32, i32]), "pt_gbuffer_get_chain": (i32, [vp, i64]),
         "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
     }
@@ -272,6 +277,21 @@ def temporal_default_params(**kw) -> _TemporalParams:
             raise TypeError(f"unknown temporal parameter {k}")
         setattr(t, k, v)
     return t
+
+
+class _RegressParams(ctypes.Structure):
+    _fields_ = [("ridge", ctypes.c_float), ("demodulate_albedo", ctypes.c_int32)]
+
+
+def regress_default_params(**kw) -> _RegressParams:
+    """pt_regress_params with overrides (ridge, demodulate_albedo)."""
+    p = _RegressParams()
+    lib.pt_regress_default_params(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(_RegressParams._fields_):
+            raise TypeError(f"unknown regress parameter {k}")
+        setattr(p, k, v)
+    return p
 
 
 class _TextureC(ctypes.Structure):
@@ -548,6 +568,25 @@ class PathTracer:
         out = {k: np.empty((self.height, self.width, 4), np.float32)
                for k in ("base_color", "base_moments", "color", "moments")}
         _check(lib.pt_temporal_get(*(out[k].ctypes.data for k in out), self.pixels), "pt_temporal_get")
+        return out
+
+    # ---- feature regression (include/pt/pt_denoise_regress.h) ----
+    def denoise_regress(self, samples: int, pbo_device_ptr: int | None = None, **params) -> np.ndarray:
+        """The accumulated image / samples through the blockwise feature regression, fitted to the
+        captured feature buffer: (h, w, 3) float32.  params: ridge, demodulate_albedo.  The
+        accumulated image is not written."""
+        p = regress_default_params(**params)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        _check(lib.pt_denoise_regress(ctypes.byref(p), int(samples), pbo_device_ptr, out.ctypes.data),
+               "pt_denoise_regress")
+        return out
+
+    def regress_blocks(self) -> np.ndarray:
+        """The last denoise_regress call's block table: (ceil(h/16) + 1, ceil(w/16) + 1, 37) float32,
+        per block n | lo.xyz | hi.xyz | beta[10][3] (see pt_regress_get)."""
+        nby, nbx = (self.height + 15) // 16 + 1, (self.width + 15) // 16 + 1
+        out = np.empty((nby, nbx, REGRESS_BLOCK_FLOATS), np.float32)
+        _check(lib.pt_regress_get(out.ctypes.data, nby * nbx), "pt_regress_get")
         return out
 
     # ---- single-kernel entry points (tests) ----

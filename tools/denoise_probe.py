@@ -3,6 +3,7 @@
     python tools/denoise_probe.py [out.json]        (default profiles/denoise_probe.json)
     python tools/denoise_probe.py --temporal [out.json]   (default profiles/denoise_temporal_probe.json)
     python tools/denoise_probe.py --through [out.json]    (default profiles/gbuffer_through_probe.json)
+    python tools/denoise_probe.py --regress [out.json]    (default profiles/denoise_regress_probe.json)
 
 8 spp are accumulated, then 5 warm-up and 20 timed calls each of pt_gbuffer_capture and of
 pt_denoise without the host copy (default parameters: 5 levels), timed by HIP events on the
@@ -20,6 +21,11 @@ pt_denoise's time beside them.
 surface) and cornell_glass_test: every iteration times pt_gbuffer_capture and
 pt_gbuffer_capture_through with K = 0 and K = 4 in turn, interleaved in one process; the record holds
 the medians, and the pixels that followed 1..4 delta surfaces.
+
+--regress: the feature regression (include/pt/pt_denoise_regress.h) at 800^2 on cornell and
+cornell_glass_test, default parameters: every iteration runs pt_denoise_regress and pt_denoise on the
+same image and capture, interleaved in one process; the record holds the medians of k_regress_fit,
+k_regress_apply and pt_denoise's five levels.
 """
 import ctypes
 import json
@@ -125,13 +131,42 @@ def probe_through(scene, res):
             "capture_ms_min_max": {k: [min(v), max(v)] for k, v in rows.items()}}
 
 
+def probe_regress(scene, res):
+    sc = ptamd.SceneFile(os.path.join(REPO, "scenes", scene + ".json"), res=(res, res))
+    tr = ptamd.PathTracer(sc)
+    L = ptamd.lib
+    tr.trace_frames(1, SPP)
+    tr.synchronize()
+    tr.capture_gbuffer(1)
+    assert L.pt_debug_denoise_timing(1) == 0
+    rows = []
+    fit, app, d = (ctypes.c_float() for _ in range(3))
+    for k in range(WARMUP + CALLS):
+        assert L.pt_denoise_regress(None, SPP, None, None) == 0, L.pt_last_error()
+        assert L.pt_debug_regress_times(ctypes.byref(fit), ctypes.byref(app)) == 0
+        assert L.pt_denoise(None, SPP, None, None) == 0, L.pt_last_error()
+        assert L.pt_debug_denoise_times(None, ctypes.byref(d), None) == 0
+        if k >= WARMUP:
+            rows.append((fit.value, app.value, fit.value + app.value, d.value))
+    L.pt_debug_denoise_timing(0)
+    blocks = tr.regress_blocks()
+    tr.free()
+    med = [statistics.median(c) for c in zip(*rows)]
+    return {"scene": scene, "res": [res, res], "spp": SPP, "warmup": WARMUP, "calls": CALLS,
+            "blocks": [blocks.shape[1], blocks.shape[0]], "blocks_with_fit": int((blocks[..., 0] > 0).sum()),
+            "fit_ms": med[0], "apply_ms": med[1], "regress_total_ms": med[2], "pt_denoise_ms": med[3],
+            "min_max": [[min(c), max(c)] for c in zip(*rows)]}
+
+
 def main():
-    modes = {"--temporal": "denoise_temporal_probe.json", "--through": "gbuffer_through_probe.json"}
+    modes = {"--temporal": "denoise_temporal_probe.json", "--through": "gbuffer_through_probe.json",
+             "--regress": "denoise_regress_probe.json"}
     args = [a for a in sys.argv[1:] if a not in modes]
     mode = next((a for a in sys.argv[1:] if a in modes), "")
     out = args[0] if args else os.path.join(REPO, "profiles", modes.get(mode, "denoise_probe.json"))
     runs = {"--temporal": lambda: [probe_temporal(800)],
             "--through": lambda: [probe_through("cornell", 800), probe_through("cornell_glass_test", 800)],
+            "--regress": lambda: [probe_regress("cornell", 800), probe_regress("cornell_glass_test", 800)],
             "": lambda: [probe(800), probe(1600)]}[mode]()
     rec = {"tool": ("tools/denoise_probe.py " + mode).strip(),
            "timer": "HIP events on the context's stream, no host copy",
