@@ -39,3 +39,7 @@ void pathtraceDenoiseTemporal(float* out);
 // the next pathtraceInit; options set through pathtraceSetOptions must then ask for
 // PT_PIPELINE_STAGED (the defaults do).  The environment variable PT_NAIVE_MESH=1 does the same.
 void pathtraceSetNaiveMesh(bool enabled);
+// Framework addition: primitive intersection through a 4-wide hierarchy over the geoms, pt_set_geom_bvh
+// of pt/pt_geom_bvh.h (min_geoms <= 0: the default threshold, 65).  Takes effect at the next
+// pathtraceInit; same images.  The environment variable PT_GEOM_BVH does the same.
+void pathtraceSetGeomBvh(bool enabled, int min_geoms = 0);

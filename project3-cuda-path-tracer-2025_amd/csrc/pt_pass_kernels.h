@@ -287,6 +287,7 @@ __global__ __launch_bounds__(BLOCK) void k_bounce(SceneDev sc, PathBuf in, PathB
                                                   QueueBuf q) {
     // dynamic LDS: [geom table, sc.num_geoms <= LDS_GEOMS, candidate-queue variants]
     //              [HAS_BVH && !SPLIT: traversal stack, stack_depth x BLOCK ints]
+    //              [VAR_GEOM_BVH: the geom hierarchy's stack, c_gbvh.stack_entries x BLOCK ints; no geom table]
     //              [VAR_WAVE_REDIST: one WaveLds per wave]
     extern __shared__ float4 s_dyn[];
     const int iter = ctl->iter;
@@ -309,13 +310,15 @@ __global__ __launch_bounds__(BLOCK) void k_bounce(SceneDev sc, PathBuf in, PathB
     constexpr bool BVH_FAST = (VAR & VAR_BVH_FAST) != 0;
     // split: the launcher guarantees the pair layout and an LDS geom table (queue or redist)
     constexpr bool SPLIT = HAS_BVH && BVH_FAST && (VAR & VAR_BVH_SPLIT) && (QUEUE || REDIST);
+    constexpr bool GBVH = (VAR & VAR_GEOM_BVH) != 0;   // pt/pt_geom_bvh.h (never with SPLIT: effective_variant)
+    static_assert(!(GBVH && SPLIT), "VAR_GEOM_BVH excludes VAR_BVH_SPLIT");
     uint64_t tc = TIMING ? sec_clock() : 0;
     const int tid = threadIdx.x;
-    const bool lds_geoms = (QUEUE || REDIST) && sc.num_geoms <= LDS_GEOMS;
+    const bool lds_geoms = !GBVH && (QUEUE || REDIST) && sc.num_geoms <= LDS_GEOMS;
     DevGeomHot* s_geoms = reinterpret_cast<DevGeomHot*>(s_dyn);
     int* s_stack = reinterpret_cast<int*>(s_dyn + (lds_geoms ? lds_geom_f4(sc) : 0));
-    WaveLds* s_wave_isect =
-        reinterpret_cast<WaveLds*>(s_stack + (HAS_BVH && !SPLIT ? sc.stack_depth * BLOCK : 0)) + (tid >> 6);
+    int* s_gstack = s_stack + (HAS_BVH && !SPLIT ? sc.stack_depth * BLOCK : 0);
+    WaveLds* s_wave_isect = reinterpret_cast<WaveLds*>(s_gstack + (GBVH ? c_gbvh.stack_entries * BLOCK : 0)) + (tid >> 6);
     const int gid = block_start + tid;
     bool active = gid < n;
     PathReg p;
@@ -364,6 +367,8 @@ __global__ __launch_bounds__(BLOCK) void k_bounce(SceneDev sc, PathBuf in, PathB
         } else if (REDIST && lds_geoms) {
             h = finish_hit<HAS_BVH, BVH_FAST>(sc, p.o, p.d, s_stack + tid, qt, qw, qs);
             PT_HOOK(DUP_HIT, HAS_BVH, BVH_FAST, sc, p.o, p.d, s_stack + tid, qt, qw, qs);
+        } else if (GBVH) {
+            h = intersect_scene_gbvh<HAS_BVH, BVH_FAST>(sc, c_gbvh, p.o, p.d, s_stack + tid, s_gstack + tid);
         } else {
             h = lds_geoms ? intersect_scene_q<HAS_BVH, TIMING, BVH_FAST, FIRST>(sc, s_geoms, p.o, p.d, s_stack + tid)
                           : intersect_scene<HAS_BVH, BVH_FAST>(sc, p.o, p.d, s_stack + tid);

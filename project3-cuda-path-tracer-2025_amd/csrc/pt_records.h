@@ -34,6 +34,8 @@ enum : int {
     VAR_NO_TEX = 1024,     // host-set: no material samples a texture or bump map, so the fused kernels'
                            // shading is compiled without the texel fetches (whose registers otherwise set
                            // the kernels' VGPR count and occupancy)
+    VAR_GEOM_BVH = 2048,   // host-set (pt/pt_geom_bvh.h): the primitive winner comes from the 4-wide hierarchy
+                           // over the geoms (intersect_prims_bvh); no LDS geom table, no split, no k_head / k_tail
     // pt_default_options: fastest in the in-process A/B (tools/ab_variants.py); every variant is bit-identical
     VAR_DEFAULT = VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BVH_SPLIT | VAR_BLOCK_REDIST,
 };
@@ -102,6 +104,19 @@ struct DevCull {
     float _pad;
 };
 static_assert(sizeof(DevCull) == 48, "DevCull");
+
+// One node of the hierarchy over the geoms' conservative boxes (host/geom_bvh.cpp builds it,
+// intersect_prims_bvh walks it): up to four children, structure-of-arrays, in ONE 128-byte line read
+// as float4 [0..2] lo.x / lo.y / lo.z of children 0..3, [3..5] hi.x / hi.y / hi.z, [6] refs, [7] spare.
+// ref >= 0: a node; ref < 0: the complement of a geom index.  An empty slot has the inverted box
+// lo = +inf, hi = -inf (and ref INT32_MIN); the traversal recognises it by lo.x > hi.x.
+struct DevGeomNode {
+    float lo[3][4];
+    float hi[3][4];
+    int32_t ref[4];
+    float spare[4];
+};
+static_assert(sizeof(DevGeomNode) == 128, "DevGeomNode");
 
 // 64-byte material: only what shading reads (sceneStructs.h:36-57)
 struct DevMaterial {

@@ -44,6 +44,7 @@
 #include "pt/pt_denoise_temporal.h"
 #include "pt/pt_gbuffer_through.h"
 #include "pt/pt_naive_mesh.h"
+#include "pt/pt_geom_bvh.h"
 #include "pt_kernels.h"
 #include "pt_denoise_kernels.h"
 #include "pt_gbuffer_through_kernels.h"
@@ -60,6 +61,7 @@ using namespace ptd;
 // =============================================================================================
 // kernels (global scope, after the using-directive above)
 // =============================================================================================
+#include "pt_geom_bvh_kernels.h"
 #include "pt_pass_kernels.h"
 #include "pt_staged_kernels.h"
 
@@ -131,9 +133,42 @@ static bool naive_next() {
     return g_naive_next != 0;
 }
 
+// the geom hierarchy (pt/pt_geom_bvh.h): what the next pt_init uses; g_gbvh_next < 0 until first
+// asked, then PT_GEOM_BVH from the environment or what pt_set_geom_bvh stored
+static int g_gbvh_next = -1, g_gbvh_min = LDS_GEOMS + 1;
+static bool gbvh_next() {
+    if (g_gbvh_next < 0) {
+        const char* e = getenv("PT_GEOM_BVH");
+        const long v = e ? strtol(e, nullptr, 10) : 0;
+        g_gbvh_next = v >= 1 ? 1 : 0;
+        g_gbvh_min = v > 1 ? (int)std::min<long>(v, 1 << 30) : LDS_GEOMS + 1;
+    }
+    return g_gbvh_next != 0;
+}
+
 extern "C" {
 
 int32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+int32_t pt_set_geom_bvh(int32_t enabled, int32_t min_geoms) {
+    g_gbvh_next = enabled ? 1 : 0;
+    g_gbvh_min = min_geoms > 0 ? min_geoms : LDS_GEOMS + 1;
+    return PT_OK;
+}
+int32_t pt_get_geom_bvh(int32_t* next_enabled, int32_t* next_min, int32_t* active) {
+    const bool on = gbvh_next();
+    if (next_enabled) *next_enabled = on ? 1 : 0;
+    if (next_min) *next_min = g_gbvh_min;
+    if (active) *active = (g_primary.inited && g_primary.gbvh_active) ? 1 : 0;
+    return PT_OK;
+}
+int32_t pt_debug_geom_bvh_info(int32_t* num_nodes, int32_t* height, int32_t* stack_entries) {
+    const bool on = g_primary.inited && g_primary.gbvh_active;
+    if (num_nodes) *num_nodes = on ? g_primary.gbvh.num_nodes : 0;
+    if (height) *height = on ? g_primary.gbvh.height : 0;
+    if (stack_entries) *stack_entries = on ? g_primary.gbvh.stack_entries : 0;
+    return PT_OK;
+}
 
 int32_t pt_set_naive_mesh(int32_t enabled) {
     g_naive_next = enabled ? 1 : 0;
@@ -288,6 +323,14 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
                         : gp->tune.bvh_max_height == 0
                             ? (1 << 30)
                             : (int)(163840 / ((size_t)BVH_WAVES * BLOCK * sizeof(int))) - 1;
+    // the geom hierarchy: one unsharded context outside the naive mode; its LDS stack shares the
+    // block's 64 KB with the mesh traversal's and, with material sort on the fused pipeline, with
+    // the regrouping exchange
+    const bool gbvh_wanted = gbvh_next() && !naive && o.shard_mode == PT_SHARD_NONE && o.num_devices <= 1;
+    lp.geom_bvh_min = gbvh_wanted ? g_gbvh_min : 0;
+    lp.geom_bvh_stack_budget =
+        (int)((65536 - (o.material_sort && o.pipeline == PT_PIPELINE_FUSED ? mat_group_lds(true, false) : 0)) /
+              (BLOCK * sizeof(int)));
     pth::SceneLayout L;
     {
         std::string err;
@@ -306,6 +349,7 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     gp->split = gp->has_bvh && !L.pairs.empty() && o.pipeline == PT_PIPELINE_FUSED && (o.variant & VAR_BVH_SPLIT) &&
               (o.variant & VAR_BVH_FAST) && (o.variant & (VAR_CAND_QUEUE | VAR_WAVE_REDIST)) &&
               s->num_geoms <= LDS_GEOMS;
+    gp->gbvh_active = !L.geom_bvh.nodes.empty();   // the fused pipeline: if its variant is compiled, below
     // MATERIAL_SORTING on the fused pipeline: the block-local regrouping by material (VAR_MAT_GROUP;
     // keys are the material ids, at most MG_KEYS - 1 of them), for the kernel variants built with it
     if (o.material_sort && o.pipeline == PT_PIPELINE_FUSED && s->num_materials <= MG_KEYS - 1 &&
@@ -314,6 +358,11 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
         o.variant |= VAR_MAT_GROUP;
         gp->opts.variant = o.variant;
     }
+    // a variant without a geom-hierarchy instantiation runs the flat path (a speed hint, not a switch)
+    if (gp->gbvh_active && o.pipeline == PT_PIPELINE_FUSED &&
+        !(variant_compiled(effective_variant(true, o.variant)) && variant_compiled(effective_variant(false, o.variant))))
+        gp->gbvh_active = false;
+    if (gp->gbvh_active) gp->split = false;   // mesh rays are not split off: no traversal queue
     if (o.pipeline == PT_PIPELINE_FUSED) {
         for (int first = 0; first < 2; ++first) {
             const int v = effective_variant(first != 0, o.variant);
@@ -356,6 +405,12 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     RC(to_device(&gp->d_leaf9, L.leaf9));
     RC(to_device(&gp->d_quads, L.quads));
     RC(to_device(&gp->d_naive_hot, L.naive_hot));
+    if (gp->gbvh_active) {
+        RC(to_device(&gp->d_gbvh, L.geom_bvh.nodes));
+        gp->gbvh = GeomBvhDev{reinterpret_cast<const float4*>(gp->d_gbvh), (int)L.geom_bvh.nodes.size(), L.geom_bvh.height,
+                              L.geom_bvh.stack_entries};
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_gbvh), &gp->gbvh, sizeof(GeomBvhDev)));
+    }
     // textures (pathtrace.cu:169-201): RGBA8 texels of every texture in one buffer
     int num_tex = 0;
     if (s->num_textures > 0 && s->textures) {

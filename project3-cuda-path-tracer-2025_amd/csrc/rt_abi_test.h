@@ -50,7 +50,9 @@ int32_t pt_test_intersect(const pt_path_segment* paths, int64_t n, pt_shadeable_
         uvd1 = tmp.p[1];
     }
     HitBuf hits{gp->d_hit_nt, gp->d_hit_mat, uvd0, uvd1};
-    if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
+    if (gp->gbvh_active)   // as both pipelines find the primitive winner in this mode
+        launch_intersect_gbvh(1, dim3(nblocks((int)n)), pathbuf(0), hits, staged_count(0));
+    else if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
         hipLaunchKernelGGL((k_intersect<true, true>), dim3(nblocks((int)n)), dim3(BLOCK), gp->bvh_lds, gp->stream, gp->sc,
                            pathbuf(0), hits, staged_count(0));
     else if (gp->has_bvh)

@@ -87,6 +87,10 @@ struct State {
     DevTriCold* d_cold = nullptr;
     bool naive = false;              // NAIVE_MESH_LOADING mode (pt/pt_naive_mesh.h): k_naive_mesh, no BVH
     DevTriHot* d_naive_hot = nullptr;    // its triangle-ordered positions (allocated in that mode only)
+    // the hierarchy over the geoms (pt/pt_geom_bvh.h); gbvh_active: this context launches its kernels
+    DevGeomNode* d_gbvh = nullptr;
+    GeomBvhDev gbvh{};
+    bool gbvh_active = false;
     float4* d_path[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     float4* d_hit_nt = nullptr;
     int* d_hit_mat = nullptr;

@@ -23,13 +23,19 @@
 // ... and those also built without texture fetches (VAR_NO_TEX: no textured / bump-mapped
 // material): the default variants with their section-counter and material-grouping forms
 #define PT_FUSED_VARIANTS_NO_TEX(X, P) P(18) P(22) P(50) P(54) P(154) P(158) P(186) P(190) X(530) X(562) X(666) X(698)
+// ... and those built with the hierarchy over the geoms (VAR_GEOM_BVH, pt/pt_geom_bvh.h), each with
+// and without texture fetches: the default variant's camera and later bounces (18, 154: never split,
+// effective_variant) and their material-grouping forms
+#define PT_FUSED_VARIANTS_GBVH(X, P) P(18) P(154) X(530) X(666)
 #ifdef PT_VAR_PROBE
 #define PT_VARIANT_SKIP(v)
 #define PT_EACH_VARIANT(F) PT_FUSED_VARIANTS(PT_VARIANT_SKIP, F)
 #define PT_EACH_VARIANT_NO_TEX(F) PT_FUSED_VARIANTS_NO_TEX(PT_VARIANT_SKIP, F)
+#define PT_EACH_VARIANT_GBVH(F) PT_FUSED_VARIANTS_GBVH(PT_VARIANT_SKIP, F)
 #else
 #define PT_EACH_VARIANT(F) PT_FUSED_VARIANTS(F, F)
 #define PT_EACH_VARIANT_NO_TEX(F) PT_FUSED_VARIANTS_NO_TEX(F, F)
+#define PT_EACH_VARIANT_GBVH(F) PT_FUSED_VARIANTS_GBVH(F, F)
 #endif
 
 // Is this effective variant one of the table's?  3 is: it was instantiated all along and init_one
@@ -43,10 +49,13 @@ bool variant_compiled(int v) {
     switch (v) {
 #define PT_LISTED(n) case n:
 #define PT_LISTED_NO_TEX(n) case VAR_NO_TEX + n:
+#define PT_LISTED_GBVH(n) case VAR_GEOM_BVH + n: case VAR_GEOM_BVH + VAR_NO_TEX + n:
         PT_EACH_VARIANT(PT_LISTED)
         PT_EACH_VARIANT_NO_TEX(PT_LISTED_NO_TEX)
+        PT_EACH_VARIANT_GBVH(PT_LISTED_GBVH)
 #undef PT_LISTED
 #undef PT_LISTED_NO_TEX
+#undef PT_LISTED_GBVH
             return true;
         default: return false;
     }
@@ -60,6 +69,9 @@ void with_flag(bool on, F&& f) {
     else f(std::false_type{});
 }
 
+// bytes of the geom hierarchy's LDS stack (c_gbvh.stack_entries x BLOCK ints on the device)
+size_t gbvh_stack_bytes() { return (size_t)gp->gbvh.stack_entries * BLOCK * sizeof(int); }
+
 // bytes of the block's LDS geom table (lds_geom_f4 on the device)
 size_t geom_table_lds() {
     return (sizeof(DevGeomHot) + (gp->sc.grid ? sizeof(DevCull) : 0)) * (size_t)gp->sc.num_geoms;
@@ -71,13 +83,14 @@ const int* staged_count(int b) { return &gp->d_ctl->cnt[b][0][0]; }
 template <bool FIRST, bool HAS_BVH, int VAR>
 void launch_bounce_t(dim3 grid, PathBuf in, PathBuf out, int b) {
     constexpr bool SPLIT = HAS_BVH && (VAR & VAR_BVH_SPLIT);
-    const bool lds = (VAR & (VAR_CAND_QUEUE | VAR_WAVE_REDIST)) && gp->sc.num_geoms <= LDS_GEOMS;
+    constexpr bool GBVH = (VAR & VAR_GEOM_BVH) != 0;   // no LDS geom table: the hierarchy's stack instead
+    const bool lds = !GBVH && (VAR & (VAR_CAND_QUEUE | VAR_WAVE_REDIST)) && gp->sc.num_geoms <= LDS_GEOMS;
     const size_t geom_lds = lds ? geom_table_lds() : 0;
     // the exchange's region: block_intersect's BlockLds, or one WaveLds per wave (wave_intersect)
     const size_t redist_lds = (VAR & VAR_WAVE_REDIST) && lds
                                   ? ((VAR & VAR_BLOCK_REDIST) ? sizeof(BlockLds) : sizeof(WaveLds) * (BLOCK / 64))
                                   : 0;
-    const size_t stack_lds = HAS_BVH && !SPLIT ? gp->bvh_lds : 0;
+    const size_t stack_lds = (HAS_BVH && !SPLIT ? gp->bvh_lds : 0) + (GBVH ? gbvh_stack_bytes() : 0);
     // VAR_MAT_GROUP's exchange reuses the exact-test exchange's region (it runs after it)
     const size_t xchg_lds = (VAR & VAR_MAT_GROUP) ? std::max(redist_lds, mat_group_lds(HAS_BVH, false)) : redist_lds;
     // tools: unused LDS added to k_bounce / the traversal kernel (occupancy A/B)
@@ -85,7 +98,7 @@ void launch_bounce_t(dim3 grid, PathBuf in, PathBuf out, int b) {
     launch(100 + b, k_bounce<FIRST, HAS_BVH, VAR>, grid, dim3(BLOCK), geom_lds + stack_lds + xchg_lds + bounce_pad, gp->sc,
            in, out, gp->d_ctl, gp->d_image, b, gp->seg_stride, gp->queue);
     const size_t lds_pad = gp->tune.bvh_lds_pad;
-    if (SPLIT) {
+    if constexpr (!GBVH) if (SPLIT) {   // (never split with the geom hierarchy: no traversal kernels for it)
         const size_t stack_bytes = (size_t)gp->sc.stack_lds * BLOCK * sizeof(int);
         // the handed-over stacks were sized for the pair tree of the allocation (ensure_frames)
         if (gp->tail_lanes > 0 && gp->sc.stack_lds > gp->tail_depth) gp->tail_lanes = 0;
@@ -111,23 +124,32 @@ void launch_bounce_v(int var, dim3 grid, PathBuf in, PathBuf out, int b) {
     switch (var) {
 #define PT_CASE(v) case v: launch_bounce_t<FIRST, HAS_BVH, v>(grid, in, out, b); break;
 #define PT_CASE_NO_TEX(v) case VAR_NO_TEX + v: launch_bounce_t<FIRST, HAS_BVH, VAR_NO_TEX + v>(grid, in, out, b); break;
+#define PT_CASE_GBVH(v)                                                                                     \
+    case VAR_GEOM_BVH + v: launch_bounce_t<FIRST, HAS_BVH, VAR_GEOM_BVH + v>(grid, in, out, b); break;          \
+    case VAR_GEOM_BVH + VAR_NO_TEX + v:                                                                         \
+        launch_bounce_t<FIRST, HAS_BVH, VAR_GEOM_BVH + VAR_NO_TEX + v>(grid, in, out, b);                       \
+        break;
         PT_EACH_VARIANT(PT_CASE)
         PT_EACH_VARIANT_NO_TEX(PT_CASE_NO_TEX)
+        PT_EACH_VARIANT_GBVH(PT_CASE_GBVH)
 #undef PT_CASE
 #undef PT_CASE_NO_TEX
+#undef PT_CASE_GBVH
         default: break;   // unreachable: pt_init refuses what variant_compiled does not list
     }
 }
 // the fused kernel's template variant for a bounce: the requested bits minus what this bounce /
 // scene does not use
 int effective_variant(bool first, int var) {
-    var &= ~(VAR_BVH_NODES | VAR_NO_TEX);   // host-only bits (layout choice; texture-free build: below)
+    var &= ~(VAR_BVH_NODES | VAR_NO_TEX | VAR_GEOM_BVH);   // host-only bits (layout choice; texture-free
+                                                           // build, geom hierarchy: below)
     // camera rays of neighbouring pixels share their candidates: redistribution only costs there
     // (A/B: bounce 0 0.164 -> 0.174 ms, bounces 1-7 ~6 % faster)
     if (first) var &= ~(VAR_WAVE_REDIST | VAR_BLOCK_REDIST);
     // tools: PT_SECTIONS_SKIP_CAMERA=1 leaves the camera bounce out of the section counters
     if (first && gp->tune.sections_skip_camera) var &= ~VAR_SECTION_TIMING;
     if (!gp->split) var &= ~VAR_BVH_SPLIT;
+    if (gp->gbvh_active) var = (var & ~VAR_BVH_SPLIT) | VAR_GEOM_BVH;   // pt_init: only where that is compiled
     // the texture-free build exists for the default variants (and their section-counter and
     // material-grouping forms); other variants keep the texture code
     if (gp->no_tex && variant_compiled(var | VAR_NO_TEX)) var |= VAR_NO_TEX;
@@ -142,6 +164,20 @@ void launch_bounce(bool first, bool bvh, int var, dim3 grid, PathBuf in, PathBuf
         if (bvh) launch_bounce_v<false, true>(var, grid, in, out, b);
         else launch_bounce_v<false, false>(var, grid, in, out, b);
     }
+}
+
+// the staged intersection stage through the geom hierarchy (k_intersect's three forms)
+void launch_intersect_gbvh(int kind, dim3 grid, PathBuf in, HitBuf hits, const int* n_in) {
+    const size_t lds = (gp->has_bvh ? gp->bvh_lds : 0) + gbvh_stack_bytes();
+    if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
+        launch(kind, k_intersect_gbvh<true, true>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
+               hits.uvd1, n_in);
+    else if (gp->has_bvh)
+        launch(kind, k_intersect_gbvh<true, false>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
+               hits.uvd1, n_in);
+    else
+        launch(kind, k_intersect_gbvh<false, false>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
+               hits.uvd1, n_in);
 }
 
 // stable compaction of the n_in paths of `pi` into `po` (three launches, see k_compact_*)
@@ -167,14 +203,15 @@ bool head_fused() {
     constexpr int V0 = VAR_CAND_QUEUE | VAR_BVH_FAST;
     constexpr int V1 = VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BLOCK_REDIST;
     const int var = gp->opts.variant & ~VAR_BVH_NODES;
-    return gp->tune.head_fuse && gp->opts.pipeline == PT_PIPELINE_FUSED && !gp->has_bvh &&
+    return gp->tune.head_fuse && gp->opts.pipeline == PT_PIPELINE_FUSED && !gp->has_bvh && !gp->gbvh_active &&
            gp->sc.num_geoms <= LDS_GEOMS && gp->sc.trace_depth >= 2 &&
            (effective_variant(true, var) & ~VAR_NO_TEX) == V0 && (effective_variant(false, var) & ~VAR_NO_TEX) == V1;
 }
 int tail_from(int batch) {
     const int depth = gp->sc.trace_depth;
     const bool lds = gp->sc.num_geoms <= LDS_GEOMS;
-    if (gp->tune.tail_off || (batch != 1 && !gp->tune.tail_any_batch) || gp->has_bvh || !lds || depth < 3 ||
+    if (gp->tune.tail_off || (batch != 1 && !gp->tune.tail_any_batch) || gp->has_bvh || gp->gbvh_active || !lds ||
+        depth < 3 ||
         (effective_variant(false, gp->opts.variant) & ~VAR_NO_TEX) !=
             (VAR_CAND_QUEUE | VAR_WAVE_REDIST | VAR_BVH_FAST | VAR_BLOCK_REDIST))
         return 0;
@@ -225,7 +262,9 @@ int enqueue_pass_body(int batch) {
         // compaction off: paths never move, every bounce sees all of them (pathtrace.cu:690)
         const int* n_in = gp->opts.stream_compaction ? staged_count(b) : staged_count(0);
         HitBuf hits{gp->d_hit_nt, gp->d_hit_mat, gp->d_hit_uvd0, gp->d_hit_uvd1};
-        if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
+        if (gp->gbvh_active)
+            launch_intersect_gbvh(1, dim3(nb), pathbuf(cur), hits, n_in);
+        else if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
             launch(1, k_intersect<true, true>, dim3(nb), dim3(BLOCK), gp->bvh_lds, gp->sc, pathbuf(cur), hits, n_in);
         else if (gp->has_bvh)
             launch(1, k_intersect<true, false>, dim3(nb), dim3(BLOCK), gp->bvh_lds, gp->sc, pathbuf(cur), hits, n_in);

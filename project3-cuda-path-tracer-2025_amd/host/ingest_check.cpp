@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -225,11 +226,13 @@ static bool parse_param(const std::string& kv, pth::LayoutParams& p) {
     else if (k == "bvh_quad") p.bvh_quad = x;
     else if (k == "grid") p.grid = x;
     else if (k == "sah_max_height") p.sah_max_height = x;
+    else if (k == "geom_bvh_min") p.geom_bvh_min = x;
+    else if (k == "geom_bvh_stack_budget") p.geom_bvh_stack_budget = x;
     else return false;
     return true;
 }
 
-static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p) {
+static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p, const char* gbvh_out = nullptr) {
     pth::SceneLayout l;
     std::string err;
     const int rc = pth::build_scene_layout(v, p, l, err);
@@ -260,16 +263,39 @@ static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p) {
         std::printf("scalar cull_extent %016llx\n", ce);
         std::printf("scalar grid_lo %08x %08x %08x\nscalar grid_inv %08x %08x %08x\n", fbits(l.grid_lo[0]),
                     fbits(l.grid_lo[1]), fbits(l.grid_lo[2]), fbits(l.grid_inv[0]), fbits(l.grid_inv[1]), fbits(l.grid_inv[2]));
+        if (!l.geom_bvh.nodes.empty()) {   // only when the tree was built: the other cases' output is unchanged
+            print_buf("geom_bvh", l.geom_bvh.nodes);
+            std::printf("scalar geom_bvh_height %d\nscalar geom_bvh_stack %d\n", l.geom_bvh.height,
+                        l.geom_bvh.stack_entries);
+        }
+        if (gbvh_out) {   // the node array as raw bytes (an empty file: no tree)
+            std::FILE* f = std::fopen(gbvh_out, "wb");
+            const size_t nn = l.geom_bvh.nodes.size();
+            if (!f || (nn && std::fwrite(l.geom_bvh.nodes.data(), sizeof(ptd::DevGeomNode), nn, f) != nn)) {
+                std::fprintf(stderr, "cannot write %s\n", gbvh_out);
+                if (f) std::fclose(f);
+                return 2;
+            }
+            std::fclose(f);
+        }
     }
     std::printf("rc=%d err=%s\n", rc, err.c_str());
     return rc;
 }
 
-// `layout FILE.json [key=value ...]` (kind null) / `layout-mutate FILE.json KIND`
-static int check_layout(const char* path, const char* kind, int nkv, char** kv) {
+// `layout FILE.json [key=value ...]` (kind null) / `layout-mutate FILE.json KIND` /
+// `geom-bvh FILE.json [min=N] [out=PATH] [key=value ...]` (gbvh): the layout with the geom hierarchy on
+// (min: its threshold, default 1), the node array written to PATH
+static int check_layout(const char* path, const char* kind, int nkv, char** kv, bool gbvh = false) {
     pth::LayoutParams p;
+    std::string gbvh_out;
+    if (gbvh) p.geom_bvh_min = 1;
     for (int i = 0; i < nkv; ++i)
-        if (!parse_param(kv[i], p)) {
+        if (gbvh && std::strncmp(kv[i], "out=", 4) == 0) {
+            gbvh_out = kv[i] + 4;
+        } else if (gbvh && std::strncmp(kv[i], "min=", 4) == 0) {
+            p.geom_bvh_min = std::max(1, std::atoi(kv[i] + 4));
+        } else if (!parse_param(kv[i], p)) {
             std::fprintf(stderr, "unknown layout parameter %s\n", kv[i]);
             return 2;
         }
@@ -292,7 +318,7 @@ static int check_layout(const char* path, const char* kind, int nkv, char** kv) 
         v.bvh_nodes = nodes.data();
         v.tri_indices = idx.data();
     }
-    if (ret == 0) print_layout(v, p);
+    if (ret == 0 && print_layout(v, p, gbvh_out.empty() ? nullptr : gbvh_out.c_str()) == 2) ret = 2;
     pt_scene_free(f);
     return ret;
 }
@@ -323,12 +349,13 @@ static int save_png(const char* out, int w, int h) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s scene|png FILE... | savepng OUT W H | layout FILE [key=value ...] | "
-                             "layout-mutate FILE KIND\n", argv[0]);
+                             "layout-mutate FILE KIND | geom-bvh FILE [min=N] [out=PATH]\n", argv[0]);
         return 2;
     }
     const std::string mode = argv[1];
     if (mode == "savepng" && argc == 5) return save_png(argv[2], std::atoi(argv[3]), std::atoi(argv[4])) == 0 ? 0 : 1;
     if (mode == "layout") return check_layout(argv[2], nullptr, argc - 3, argv + 3);
+    if (mode == "geom-bvh") return check_layout(argv[2], nullptr, argc - 3, argv + 3, true);
     if (mode == "layout-mutate" && argc == 4) return check_layout(argv[2], argv[3], 0, nullptr);
     for (int i = 2; i < argc; ++i) {
         std::printf("%s: ", argv[i]);

@@ -6,6 +6,7 @@
 #include "pt/pt_denoise.h"
 #include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
+#include "pt/pt_geom_bvh.h"
 #include "pt/pt_naive_mesh.h"
 
 namespace {
@@ -28,6 +29,7 @@ void pathtraceSetOptions(const pt_options& opts) {
 }
 
 void pathtraceSetNaiveMesh(bool enabled) { pt_set_naive_mesh(enabled ? 1 : 0); }
+void pathtraceSetGeomBvh(bool enabled, int min_geoms) { pt_set_geom_bvh(enabled ? 1 : 0, min_geoms); }
 
 void InitDataContainer(GuiDataContainer* imGuiData) {
     guiData = imGuiData;

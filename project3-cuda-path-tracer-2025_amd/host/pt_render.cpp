@@ -9,8 +9,10 @@
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
 //             [--denoise [LEVELS] [--denoise-through K]] [--denoise-temporal [LEVELS]] [--naive-mesh]
-//             [--denoise-regress [RIDGE]]
+//             [--denoise-regress [RIDGE]] [--geom-bvh [MIN]]
 //
+// --geom-bvh traces the cubes and spheres through a 4-wide hierarchy over them (include/pt/pt_geom_bvh.h)
+// in scenes of at least MIN geoms (default 65): same image, for scenes of many primitives.
 // --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
 // triangle in array order, no BVH.  It implies --pipeline staged.
 // --denoise writes PREFIX.denoised.png beside the ordinary output: the averaged image through the
@@ -182,11 +184,12 @@ int main(int argc, char** argv) {
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
                     "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS] [--denoise-through K]] "
-                    "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]]\n", argv[0]);
+                    "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]] [--geom-bvh [MIN]]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
     bool gpu_bvh = false, naive_mesh = false;
+    int geom_bvh_min = -1;    // -1: no --geom-bvh; 0: its default threshold
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
     int temporal_levels = 0;  // 0: no --denoise-temporal
@@ -211,6 +214,19 @@ int main(int argc, char** argv) {
         else if (a == "--device") opts.device = std::atoi(next());
         else if (a == "--gpu-bvh") gpu_bvh = true;
         else if (a == "--naive-mesh") naive_mesh = true;
+        else if (a == "--geom-bvh") {   // the threshold is optional, like --denoise's level count
+            geom_bvh_min = 0;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* v = argv[++i];
+                char* end = nullptr;
+                const long n = std::strtol(v, &end, 10);
+                if (end == v || *end != '\0' || n < 1 || n > (1 << 30)) {
+                    std::fprintf(stderr, "usage: --geom-bvh [MIN], MIN an integer >= 1, got '%s'\n", v);
+                    return 2;
+                }
+                geom_bvh_min = (int)n;
+            }
+        }
         else if (a == "--devices") {   // every frame split into pixel shards over these GPUs
             const std::string d = next();
             opts.num_devices = 0;
@@ -279,6 +295,7 @@ int main(int argc, char** argv) {
         }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (geom_bvh_min >= 0) pathtraceSetGeomBvh(true, geom_bvh_min);
     if (naive_mesh) {   // the mode runs on the staged pipeline
         pathtraceSetNaiveMesh(true);
         opts.pipeline = PT_PIPELINE_STAGED;

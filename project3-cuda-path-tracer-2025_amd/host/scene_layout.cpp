@@ -798,6 +798,13 @@ int32_t build_scene_layout(const pt_scene_view& s, const LayoutParams& p, SceneL
     const int grid_min = p.grid == 1 ? 2 : GRID_MIN_GEOMS;
     if (p.grid != 0 && s.num_geoms >= grid_min && s.num_geoms <= LDS_GEOMS)   // (false: boxes not finite, no table)
         build_candidate_table(out.culls, s.num_geoms, s.camera.position, out.grid, out.grid_lo, out.grid_inv);
+    // the hierarchy over the geoms' boxes; it stays empty (the flat loop runs) for a box that is not
+    // finite or a stack that does not fit beside the mesh traversal's
+    if (p.geom_bvh_min > 0 && s.num_geoms >= p.geom_bvh_min) {
+        build_geom_bvh(out.geoms, out.geom_bvh);
+        if (out.geom_bvh.stack_entries + (out.has_bvh ? out.stack_depth : 0) > p.geom_bvh_stack_budget)
+            out.geom_bvh = GeomBvh();
+    }
     return PT_OK;
 }
 

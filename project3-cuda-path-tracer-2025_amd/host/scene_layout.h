@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "pt/pathtrace_abi.h"
+#include "geom_bvh.h"
 #include "pt_records.h"
 
 namespace pth {
@@ -29,6 +30,11 @@ struct LayoutParams {
     int bvh_quad = 1;                   // PT_BVH_QUAD
     int grid = -1;                      // PT_GRID: 0 no candidate table, 1 also for small scenes
     int sah_max_height = 21;            // SAH tree height bound, resolved (1 << 30: none)
+    // the hierarchy over the geoms (pt/pt_geom_bvh.h): built for scenes of at least geom_bvh_min geoms
+    // (0: the mode is off) when its stack, together with the mesh traversal's, fits in
+    // geom_bvh_stack_budget LDS entries per lane (resolved by the runtime from its kernels' LDS)
+    int geom_bvh_min = 0;
+    int geom_bvh_stack_budget = 64;
 };
 
 struct SceneLayout {
@@ -58,6 +64,7 @@ struct SceneLayout {
     int root_ref = 0, pair_count = 0, ref_shift = 16;
     float4 root_lo{}, root_hi{};            // root box (hi.w: root cull size)
     double cull_extent = 1.0;
+    GeomBvh geom_bvh;                       // nodes empty: the mode is off or cannot apply
 };
 
 // PT_OK and a filled `out`, or an error code with its message in `err` (`out` is then unspecified).

@@ -124,6 +124,8 @@ REGRESS_BLOCK_FLOATS = 37   # n | lo.xyz | hi.xyz | beta[10][3]
 GBUFFER_THROUGH_SYMBOLS = ["pt_gbuffer_capture_through", "pt_gbuffer_get_chain"]
 # include/pt/pt_naive_mesh.h (the reference's NAIVE_MESH_LOADING mode)
 NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_mesh_tile"]
+# include/pt/pt_geom_bvh.h (primitive intersection through a 4-wide hierarchy over the geoms)
+GEOM_BVH_SYMBOLS = ["pt_set_geom_bvh", "pt_get_geom_bvh", "pt_debug_geom_bvh_info"]
 
 
 def _load():
@@ -173,6 +175,8 @@ def _load():
         "pt_regress_get": (i32, [vp, i64]), "pt_debug_regress_times": (i32, [vp, vp]),
         "pt_gbuffer_capture_through": (i32, [i32, i32]), "pt_gbuffer_get_chain": (i32, [vp, i64]),
         "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
+        "pt_set_geom_bvh": (i32, [i32, i32]), "pt_get_geom_bvh": (i32, [vp, vp, vp]),
+        "pt_debug_geom_bvh_info": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -231,6 +235,26 @@ def get_naive_mesh() -> tuple:
 def naive_mesh_tile() -> int:
     """Triangles per LDS tile of k_naive_mesh (tests and tools)."""
     return int(lib.pt_debug_naive_mesh_tile())
+
+
+def set_geom_bvh(enabled: bool, min_geoms: int = 0):
+    """The geom hierarchy for the NEXT pt_init (include/pt/pt_geom_bvh.h): scenes of at least
+    `min_geoms` geoms (<= 0: the default, 65) find their primitive winner through it.  Sticky."""
+    _check(lib.pt_set_geom_bvh(int(bool(enabled)), int(min_geoms)), "pt_set_geom_bvh")
+
+
+def get_geom_bvh() -> tuple:
+    """(on for the next pt_init, its threshold, the live context launches the geom-BVH kernels)."""
+    on, mn, act = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_get_geom_bvh(ctypes.byref(on), ctypes.byref(mn), ctypes.byref(act)), "pt_get_geom_bvh")
+    return bool(on.value), int(mn.value), bool(act.value)
+
+
+def geom_bvh_info() -> dict:
+    """The live context's geom hierarchy (zeros when the mode is not active)."""
+    n, h, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_debug_geom_bvh_info(ctypes.byref(n), ctypes.byref(h), ctypes.byref(s)), "pt_debug_geom_bvh_info")
+    return {"num_nodes": n.value, "height": h.value, "stack_entries": s.value}
 
 
 def load_texture(path: str) -> np.ndarray:
@@ -393,13 +417,17 @@ class PathTracer:
 
     _live = None
 
-    def __init__(self, scene, naive_mesh: bool = False, **options):
+    def __init__(self, scene, naive_mesh: bool = False, geom_bvh=False, **options):
         """`naive_mesh=True`: the reference's NAIVE_MESH_LOADING mode for this tracer
-        (pt_set_naive_mesh around pt_init; the process-wide setting is put back afterwards)."""
+        (pt_set_naive_mesh around pt_init; the process-wide setting is put back afterwards).
+        `geom_bvh=True | N`: the geom hierarchy of include/pt/pt_geom_bvh.h for this tracer, with the
+        default threshold or for scenes of at least N geoms (set and put back the same way)."""
         if PathTracer._live is not None:
             PathTracer._live.free()       # the library state is process-global, like the reference's
         prev = get_naive_mesh()[0]
+        prev_gbvh = get_geom_bvh()[:2]
         set_naive_mesh(naive_mesh)
+        set_geom_bvh(bool(geom_bvh), 0 if isinstance(geom_bvh, bool) else int(geom_bvh))
         try:
             self.opts = default_options(**options)   # after the setter: staged by default in naive mode
             view = scene.view() if hasattr(scene, "view") else scene
@@ -410,6 +438,7 @@ class PathTracer:
             _check(lib.pt_init(ctypes.byref(view), ctypes.byref(self.opts)), "pt_init")
         finally:
             set_naive_mesh(prev)
+            set_geom_bvh(*prev_gbvh)
         PathTracer._live = self
         self.iteration = 0
         self._host_image = None
