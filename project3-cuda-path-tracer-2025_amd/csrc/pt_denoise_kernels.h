@@ -83,6 +83,24 @@ struct AtrousArgs {
 
 PT_DEV bool at_finite(float v) { return v - v == 0.0f; }
 
+// c0 of pixel idx, the colour every denoiser filters: image / samples, divided by max(albedo al,
+// AT_ALBEDO_MIN) where the call demodulates (demod) and the pixel is a hit by the caller's own
+// predicate (hit).  Returns whether all three channels are finite.  For the callers that hold the
+// pixel's albedo anyway (pt_temporal_kernels.h, pt_regress_kernels.h); at_load_color below is the
+// same with the albedo loaded only where it divides.
+PT_DEV bool at_c0(const float* image, int idx, float samples, bool demod, bool hit, float4 al, float& r, float& g,
+                  float& b) {
+    r = image[3 * (size_t)idx] / samples;
+    g = image[3 * (size_t)idx + 1] / samples;
+    b = image[3 * (size_t)idx + 2] / samples;
+    if (demod && hit) {
+        r = r / __builtin_fmaxf(al.x, AT_ALBEDO_MIN);
+        g = g / __builtin_fmaxf(al.y, AT_ALBEDO_MIN);
+        b = b / __builtin_fmaxf(al.z, AT_ALBEDO_MIN);
+    }
+    return at_finite(r) && at_finite(g) && at_finite(b);
+}
+
 // the level's input colour at pixel idx
 PT_DEV float4 at_load_color(const AtrousArgs& a, int idx, float hit) {
     if (!a.first) return a.cin[idx];

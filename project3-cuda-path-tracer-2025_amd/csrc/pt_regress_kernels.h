@@ -53,14 +53,7 @@ struct RegressPixel {
 PT_DEV RegressPixel rg_pixel(const RegressArgs& a, int idx, float hit_flag, float4 al) {
     RegressPixel p;
     p.hit = hit_flag > 0.5f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p.c[k] = a.image[3 * (size_t)idx + k] / a.samples;
-    if (a.demod && p.hit) {
-        p.c[0] = p.c[0] / __builtin_fmaxf(al.x, AT_ALBEDO_MIN);
-        p.c[1] = p.c[1] / __builtin_fmaxf(al.y, AT_ALBEDO_MIN);
-        p.c[2] = p.c[2] / __builtin_fmaxf(al.z, AT_ALBEDO_MIN);
-    }
-    p.finite = at_finite(p.c[0]) && at_finite(p.c[1]) && at_finite(p.c[2]);
+    p.finite = at_c0(a.image, idx, a.samples, a.demod, p.hit, al, p.c[0], p.c[1], p.c[2]);
     const int m = (int)al.w;
     p.surface = p.hit && m >= 0 && m < a.num_mats && !(a.mats[m].emittance > 0.0f);
     return p;

@@ -75,6 +75,7 @@ namespace {
 #include "rt_pass.h"
 #include "rt_spec.h"
 #include "rt_buffers.h"
+#include "rt_denoise.h"
 
 CamDev to_camdev(const pt_camera& c) {
     CamDev d;
@@ -565,7 +566,7 @@ int32_t pt_set_camera(const pt_camera* c) {
             RC(spec_cancel());                          // traced with the old camera
             HIPCHK(hipStreamSynchronize(gp->stream));   // a replayed pass may still hold the graph
             gp->sc.cam = nc;
-            gp->gbuf_valid = false;   // the feature planes show the old camera's first hits
+            gp->dn.gbuf_valid = false;   // the feature planes show the old camera's first hits
             release_graph();   // kernel arguments changed
         }
     }

@@ -108,18 +108,10 @@ struct IntegrateArgs {
     float var_hist_min;          // temporal variance where N_base >= this
 };
 
-// c0 of pixel idx, as at_load_color forms it; returns the material
+// c0 of pixel idx (at_c0; a hit is a material >= 0 here); returns the material
 PT_DEV float tp_load_c0(const IntegrateArgs& a, int idx, float& r, float& g, float& b, bool& fin) {
     const float4 al = a.ga[idx];
-    r = a.image[3 * (size_t)idx] / a.samples;
-    g = a.image[3 * (size_t)idx + 1] / a.samples;
-    b = a.image[3 * (size_t)idx + 2] / a.samples;
-    if (a.demod && al.w >= 0.0f) {
-        r = r / __builtin_fmaxf(al.x, AT_ALBEDO_MIN);
-        g = g / __builtin_fmaxf(al.y, AT_ALBEDO_MIN);
-        b = b / __builtin_fmaxf(al.z, AT_ALBEDO_MIN);
-    }
-    fin = at_finite(r) && at_finite(g) && at_finite(b);
+    fin = at_c0(a.image, idx, a.samples, a.demod, al.w >= 0.0f, al, r, g, b);
     return al.w;
 }
 

@@ -1,24 +1,11 @@
 // rt_abi_denoise.h — the denoiser's entry points (inside pt_runtime.hip's extern "C" block).
-// Owns: pt_gbuffer_* (and which of the two plane sets a capture writes), pt_denoise*, pt_debug_denoise_*.  Calls: rt_core.h, M.n of rt_multi.h, and
-// the kernels of pt_denoise_kernels.h.
+// Owns: pt_gbuffer_* (and which of the two plane sets a capture writes), pt_denoise*, pt_debug_denoise_*.
+// Calls: rt_core.h (State::dn), with_traversal of rt_pass.h, the checks, copy_planes, result_out and
+// atrous_levels of rt_denoise.h, and the kernels of pt_denoise_kernels.h.
 
 // ---------------------------------------------------------------------------------------------
 // denoiser (include/pt/pt_denoise.h): first-hit feature planes + the a-trous filter
 // ---------------------------------------------------------------------------------------------
-static bool g_dn_timing = false;   // pt_debug_denoise_timing
-
-static int32_t denoise_ctx(const char* what) {
-    RC(need_init());
-    if (M.n > 1 || gp->opts.shard_mode != PT_SHARD_NONE)
-        return fail(PT_E_UNSUPPORTED, "%s: one unsharded device context only (num_devices > 1 or shard_mode set)", what);
-    return PT_OK;
-}
-static int32_t denoise_event(int k) {
-    if (!gp->dn_ev[k]) HIPCHK(hipEventCreate(&gp->dn_ev[k]));
-    HIPCHK(hipEventRecord(gp->dn_ev[k], gp->stream));
-    return PT_OK;
-}
-
 void pt_denoise_default_params(pt_denoise_params* p) {
     if (!p) return;
     p->levels = 5;
@@ -35,18 +22,29 @@ static int32_t capture_begin(const char* what, int32_t iteration, GBuf* g) {
     RC(denoise_ctx(what));
     if (gp->naive) return fail(PT_E_UNSUPPORTED, "%s: not available in naive mesh mode", what);
     if (iteration <= 0) return fail(PT_E_INVALID, "iteration is 1-based, got %d", iteration);
+    DenoiseState& dn = gp->dn;
     const int n = gp->pixels_total;
-    gp->gbuf_valid = false;
-    gp->gbuf_through = -1;
-    if (!gp->d_gbuf[0][0]) {
-        for (float4*& p : gp->d_gbuf[0]) RC(dalloc(&p, (size_t)n));
-        for (float4*& p : gp->d_dn_color) RC(dalloc(&p, (size_t)n));
+    dn.gbuf_valid = false;
+    dn.gbuf_through = -1;
+    if (!dn.d_gbuf[0][0]) {
+        for (float4*& p : dn.d_gbuf[0]) RC(dalloc(&p, (size_t)n));
+        for (float4*& p : dn.d_color) RC(dalloc(&p, (size_t)n));
     }
     // the temporal history (rt_abi_temporal.h) keeps the planes of its capture: write the other set
-    if (gp->tp_history && gp->tp_hist_set == gp->gbuf_cur) gp->gbuf_cur ^= 1;
-    gp->tp_base_valid = false;
-    float4* const* cur = gp->d_gbuf[gp->gbuf_cur];
+    if (dn.tp_history && dn.tp_hist_set == dn.gbuf_cur) dn.gbuf_cur ^= 1;
+    dn.tp_base_valid = false;
+    float4* const* cur = dn.d_gbuf[dn.gbuf_cur];
     *g = GBuf{cur[0], cur[1], cur[2]};
+    return PT_OK;
+}
+// ... and its end, after the capture's last launch (event 0 went before its first): the wait, the
+// capture's time, the buffer valid
+static int32_t capture_end() {
+    HIPCHK(hipGetLastError());
+    if (g_dn_timing) RC(denoise_event(gp->dn.ev, 1));
+    HIPCHK(hipStreamSynchronize(gp->stream));
+    if (g_dn_timing) HIPCHK(hipEventElapsedTime(&gp->dn.capture_ms, gp->dn.ev[0], gp->dn.ev[1]));
+    gp->dn.gbuf_valid = true;
     return PT_OK;
 }
 
@@ -54,33 +52,20 @@ int32_t pt_gbuffer_capture(int32_t iteration) {
     GBuf g;
     RC(capture_begin("pt_gbuffer_capture", iteration, &g));
     const int n = gp->pixels_total;
-    if (g_dn_timing) RC(denoise_event(0));
+    if (g_dn_timing) RC(denoise_event(gp->dn.ev, 0));
     // the traversal pt_test_intersect (and the staged pipeline) runs for this context's options
-    if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
-        hipLaunchKernelGGL((k_gbuffer<true, true>), dim3(nblocks(n)), dim3(BLOCK), gp->bvh_lds, gp->stream, gp->sc, g,
-                           iteration, n);
-    else if (gp->has_bvh)
-        hipLaunchKernelGGL((k_gbuffer<true, false>), dim3(nblocks(n)), dim3(BLOCK), gp->bvh_lds, gp->stream, gp->sc, g,
-                           iteration, n);
-    else
-        hipLaunchKernelGGL((k_gbuffer<false, false>), dim3(nblocks(n)), dim3(BLOCK), 0, gp->stream, gp->sc, g, iteration, n);
-    HIPCHK(hipGetLastError());
-    if (g_dn_timing) RC(denoise_event(1));
-    HIPCHK(hipStreamSynchronize(gp->stream));
-    if (g_dn_timing) HIPCHK(hipEventElapsedTime(&gp->dn_capture_ms, gp->dn_ev[0], gp->dn_ev[1]));
-    gp->gbuf_valid = true;
-    return PT_OK;
+    with_traversal([&](auto bvh, auto fast) {
+        hipLaunchKernelGGL((k_gbuffer<bvh.value, fast.value>), dim3(nblocks(n)), dim3(BLOCK), traversal_lds(), gp->stream,
+                           gp->sc, g, iteration, n);
+    });
+    return capture_end();
 }
 
 int32_t pt_gbuffer_get(float* normal_t, float* position, float* albedo_mat, int64_t n_pixels) {
     RC(denoise_ctx("pt_gbuffer_get"));
-    if (!gp->gbuf_valid) return fail(PT_E_STATE, "pt_gbuffer_get: no feature buffer captured for this camera");
-    if (n_pixels < gp->pixels_total) return fail(PT_E_INVALID, "pt_gbuffer_get: room for %lld pixels, the image has %d",
-                                                 (long long)n_pixels, gp->pixels_total);
+    if (!gp->dn.gbuf_valid) return fail(PT_E_STATE, "pt_gbuffer_get: no feature buffer captured for this camera");
     float* dst[3] = {normal_t, position, albedo_mat};
-    for (int k = 0; k < 3; ++k)
-        if (dst[k]) HIPCHK(smemcpy(dst[k], gp->d_gbuf[gp->gbuf_cur][k], sizeof(float4) * (size_t)gp->pixels_total, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return copy_planes("pt_gbuffer_get", n_pixels, 3, dst, gp->dn.d_gbuf[gp->dn.gbuf_cur]);
 }
 
 int32_t pt_denoise(const pt_denoise_params* params, int32_t samples, pt_uchar4* pbo, float* host_out) {
@@ -88,55 +73,25 @@ int32_t pt_denoise(const pt_denoise_params* params, int32_t samples, pt_uchar4* 
     pt_denoise_params p;
     if (params) p = *params;
     else pt_denoise_default_params(&p);
-    if (p.levels < 1 || p.levels > PT_DENOISE_MAX_LEVELS)
-        return fail(PT_E_INVALID, "pt_denoise: levels must be 1 .. %d, got %d", PT_DENOISE_MAX_LEVELS, p.levels);
-    const float sig[3] = {p.sigma_color, p.sigma_normal, p.sigma_position};
-    const char* sig_name[3] = {"sigma_color", "sigma_normal", "sigma_position"};
-    for (int k = 0; k < 3; ++k)
-        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]))
-            return fail(PT_E_INVALID, "pt_denoise: %s must be positive and finite", sig_name[k]);
-    if (samples < 1) return fail(PT_E_INVALID, "pt_denoise: samples must be >= 1, got %d", samples);
-    if (!gp->gbuf_valid)
-        return fail(PT_E_STATE, "pt_denoise: no feature buffer captured for this camera (pt_gbuffer_capture)");
-    auto inv_sq = [](double s) { return (float)std::min(1.0 / (s * s), 3.0e38); };
+    RC(check_params("pt_denoise", p));
+    RC(check_samples("pt_denoise", samples));
+    RC(check_captured("pt_denoise"));
+    DenoiseState& dn = gp->dn;
     AtrousArgs a{};
     a.image = gp->d_image;
-    a.gn = gp->d_gbuf[gp->gbuf_cur][0];
-    a.gx = gp->d_gbuf[gp->gbuf_cur][1];
-    a.ga = gp->d_gbuf[gp->gbuf_cur][2];
-    a.W = gp->width;
-    a.H = gp->height;
-    a.demod = p.demodulate_albedo != 0;
-    a.samples = (float)samples;
-    a.k_normal = inv_sq(p.sigma_normal);
-    a.k_position = inv_sq(p.sigma_position);
-    const dim3 grid((a.W + AT_TILE - 1) / AT_TILE, (a.H + AT_TILE - 1) / AT_TILE);
+    atrous_common(a, p, samples);
     float* out3 = nullptr;
-    for (int l = 0; l < p.levels; ++l) {
-        a.first = l == 0;
-        a.last = l == p.levels - 1;
-        a.step = 1 << l;
-        a.cin = l > 0 ? gp->d_dn_color[(l - 1) & 1] : nullptr;
-        a.cout = a.last ? nullptr : gp->d_dn_color[l & 1];
-        // the last level stores float3 per pixel, in the colour buffer it would have written
-        a.out3 = out3 = a.last ? reinterpret_cast<float*>(gp->d_dn_color[l & 1]) : nullptr;
-        a.pbo = a.last ? pbo : nullptr;
-        a.k_color = inv_sq((double)p.sigma_color * std::ldexp(1.0, -l));
-        if (g_dn_timing) RC(denoise_event(2 + l));
-        if (l == 0) hipLaunchKernelGGL(k_atrous_lds<1>, grid, dim3(BLOCK), 0, gp->stream, a);
-        else if (l == 1) hipLaunchKernelGGL(k_atrous_lds<2>, grid, dim3(BLOCK), 0, gp->stream, a);
-        else hipLaunchKernelGGL(k_atrous_direct, grid, dim3(BLOCK), 0, gp->stream, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (g_dn_timing) RC(denoise_event(2 + p.levels));
-    if (host_out)
-        HIPCHK(hipMemcpyAsync(host_out, out3, sizeof(float) * 3 * (size_t)gp->pixels_total, hipMemcpyDeviceToHost, gp->stream));
-    HIPCHK(hipStreamSynchronize(gp->stream));
+    RC(atrous_levels(a, nullptr, p.levels, pbo, [&](AtrousArgs& lv, int l) {
+        lv.k_color = inv_sq((double)p.sigma_color * std::ldexp(1.0, -l));
+        return g_dn_timing ? denoise_event(dn.ev, 2 + l) : (int32_t)PT_OK;
+    }, &out3));
+    if (g_dn_timing) RC(denoise_event(dn.ev, 2 + p.levels));
+    RC(result_out(host_out, out3));
     if (g_dn_timing) {
-        HIPCHK(hipEventElapsedTime(&gp->dn_ms, gp->dn_ev[2], gp->dn_ev[2 + p.levels]));
+        HIPCHK(hipEventElapsedTime(&dn.ms, dn.ev[2], dn.ev[2 + p.levels]));
         for (int l = 0; l < PT_DENOISE_MAX_LEVELS; ++l) {
-            gp->dn_level_ms[l] = 0.f;
-            if (l < p.levels) HIPCHK(hipEventElapsedTime(&gp->dn_level_ms[l], gp->dn_ev[2 + l], gp->dn_ev[3 + l]));
+            dn.level_ms[l] = 0.f;
+            if (l < p.levels) HIPCHK(hipEventElapsedTime(&dn.level_ms[l], dn.ev[2 + l], dn.ev[3 + l]));
         }
     }
     return PT_OK;
@@ -149,9 +104,9 @@ int32_t pt_debug_denoise_timing(int32_t enabled) {
 
 int32_t pt_debug_denoise_times(float* capture_ms, float* denoise_ms, float* level_ms) {
     RC(need_init());
-    if (capture_ms) *capture_ms = gp->dn_capture_ms;
-    if (denoise_ms) *denoise_ms = gp->dn_ms;
-    if (level_ms) memcpy(level_ms, gp->dn_level_ms, sizeof gp->dn_level_ms);
+    if (capture_ms) *capture_ms = gp->dn.capture_ms;
+    if (denoise_ms) *denoise_ms = gp->dn.ms;
+    if (level_ms) memcpy(level_ms, gp->dn.level_ms, sizeof gp->dn.level_ms);
     return PT_OK;
 }
 

@@ -1,17 +1,13 @@
 // rt_abi_regress.h — the feature regression's entry points (inside pt_runtime.hip's extern "C" block).
-// Owns: pt_regress_*, pt_denoise_regress, pt_debug_regress_times and State::rg_* / d_rg_tab.  Calls:
-// rt_core.h, denoise_ctx and g_dn_timing of rt_abi_denoise.h, and the kernels of pt_regress_kernels.h.
+// Owns: pt_regress_*, pt_denoise_regress, pt_debug_regress_times and DenoiseState's rg_* / d_rg_tab.
+// Calls: rt_core.h, the checks, denoise_event and result_out of rt_denoise.h, and the kernels of
+// pt_regress_kernels.h.
 
 // ---------------------------------------------------------------------------------------------
 // blockwise feature regression (include/pt/pt_denoise_regress.h)
 // ---------------------------------------------------------------------------------------------
 static_assert(RG_BLOCK_FLOATS == PT_REGRESS_BLOCK_FLOATS, "block record");
 
-static int32_t regress_event(int k) {
-    if (!gp->rg_ev[k]) HIPCHK(hipEventCreate(&gp->rg_ev[k]));
-    HIPCHK(hipEventRecord(gp->rg_ev[k], gp->stream));
-    return PT_OK;
-}
 static int regress_blocks_x() { return (gp->width + RG_STRIDE - 1) / RG_STRIDE + 1; }
 static int regress_blocks_y() { return (gp->height + RG_STRIDE - 1) / RG_STRIDE + 1; }
 
@@ -27,21 +23,20 @@ int32_t pt_denoise_regress(const pt_regress_params* params, int32_t samples, pt_
     pt_regress_params p;
     if (params) p = *params;
     else pt_regress_default_params(&p);
-    if (!(p.ridge > 0.0f) || !std::isfinite(p.ridge))
-        return fail(PT_E_INVALID, "pt_denoise_regress: ridge must be positive and finite");
-    if (samples < 1) return fail(PT_E_INVALID, "pt_denoise_regress: samples must be >= 1, got %d", samples);
-    if (!gp->gbuf_valid)
-        return fail(PT_E_STATE, "pt_denoise_regress: no feature buffer captured for this camera (pt_gbuffer_capture)");
+    RC(check_positive("pt_denoise_regress", "ridge", p.ridge));
+    RC(check_samples("pt_denoise_regress", samples));
+    RC(check_captured("pt_denoise_regress"));
+    DenoiseState& dn = gp->dn;
     const int nbx = regress_blocks_x(), nby = regress_blocks_y();
-    if (!gp->d_rg_tab) RC(dalloc(&gp->d_rg_tab, (size_t)nbx * nby * RG_REC));
+    if (!dn.d_rg_tab) RC(dalloc(&dn.d_rg_tab, (size_t)nbx * nby * RG_REC));
     RegressArgs a{};
     a.image = gp->d_image;
-    a.gn = gp->d_gbuf[gp->gbuf_cur][0];
-    a.gx = gp->d_gbuf[gp->gbuf_cur][1];
-    a.ga = gp->d_gbuf[gp->gbuf_cur][2];
+    a.gn = dn.d_gbuf[dn.gbuf_cur][0];
+    a.gx = dn.d_gbuf[dn.gbuf_cur][1];
+    a.ga = dn.d_gbuf[dn.gbuf_cur][2];
     a.mats = gp->d_mats;
-    a.tab = gp->d_rg_tab;
-    a.out3 = reinterpret_cast<float*>(gp->d_dn_color[0]);   // float3 per pixel in a float4 plane
+    a.tab = dn.d_rg_tab;
+    a.out3 = reinterpret_cast<float*>(dn.d_color[0]);   // float3 per pixel in a float4 plane
     a.pbo = pbo;
     a.W = gp->width;
     a.H = gp->height;
@@ -51,38 +46,36 @@ int32_t pt_denoise_regress(const pt_regress_params* params, int32_t samples, pt_
     a.samples = (float)samples;
     a.ridge = p.ridge;
     const bool timing = g_dn_timing;
-    if (timing) RC(regress_event(0));
+    if (timing) RC(denoise_event(dn.rg_ev, 0));
     hipLaunchKernelGGL(k_regress_fit, dim3(nbx, nby), dim3(BLOCK), 0, gp->stream, a);
     HIPCHK(hipGetLastError());
-    if (timing) RC(regress_event(1));
+    if (timing) RC(denoise_event(dn.rg_ev, 1));
     hipLaunchKernelGGL(k_regress_apply, dim3(nbx - 1, nby - 1), dim3(BLOCK), 0, gp->stream, a);
     HIPCHK(hipGetLastError());
-    if (timing) RC(regress_event(2));
-    gp->rg_result = true;
-    if (host_out)
-        HIPCHK(hipMemcpyAsync(host_out, a.out3, sizeof(float) * 3 * (size_t)gp->pixels_total, hipMemcpyDeviceToHost, gp->stream));
-    HIPCHK(hipStreamSynchronize(gp->stream));
+    if (timing) RC(denoise_event(dn.rg_ev, 2));
+    dn.rg_result = true;
+    RC(result_out(host_out, a.out3));
     if (timing)
-        for (int k = 0; k < 2; ++k) HIPCHK(hipEventElapsedTime(&gp->rg_ms[k], gp->rg_ev[k], gp->rg_ev[k + 1]));
+        for (int k = 0; k < 2; ++k) HIPCHK(hipEventElapsedTime(&dn.rg_ms[k], dn.rg_ev[k], dn.rg_ev[k + 1]));
     return PT_OK;
 }
 
 int32_t pt_regress_get(float* blocks, int64_t n_blocks) {
     RC(denoise_ctx("pt_regress_get"));
-    if (!gp->rg_result) return fail(PT_E_STATE, "pt_regress_get: pt_denoise_regress has not run");
+    if (!gp->dn.rg_result) return fail(PT_E_STATE, "pt_regress_get: pt_denoise_regress has not run");
     const int64_t nb = (int64_t)regress_blocks_x() * regress_blocks_y();
     if (!blocks || n_blocks < nb)
         return fail(PT_E_INVALID, "pt_regress_get: room for %lld blocks, the image has %lld", (long long)n_blocks, (long long)nb);
     std::vector<float> tab((size_t)nb * RG_REC);   // the records are RG_REC floats apart on the device
-    HIPCHK(smemcpy(tab.data(), gp->d_rg_tab, sizeof(float) * tab.size(), hipMemcpyDeviceToHost));
+    HIPCHK(smemcpy(tab.data(), gp->dn.d_rg_tab, sizeof(float) * tab.size(), hipMemcpyDeviceToHost));
     for (int64_t b = 0; b < nb; ++b) memcpy(blocks + b * RG_BLOCK_FLOATS, &tab[(size_t)b * RG_REC], sizeof(float) * RG_BLOCK_FLOATS);
     return PT_OK;
 }
 
 int32_t pt_debug_regress_times(float* fit_ms, float* apply_ms) {
     RC(need_init());
-    if (fit_ms) *fit_ms = gp->rg_ms[0];
-    if (apply_ms) *apply_ms = gp->rg_ms[1];
+    if (fit_ms) *fit_ms = gp->dn.rg_ms[0];
+    if (apply_ms) *apply_ms = gp->dn.rg_ms[1];
     return PT_OK;
 }
 

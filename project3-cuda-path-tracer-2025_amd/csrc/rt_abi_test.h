@@ -52,15 +52,11 @@ int32_t pt_test_intersect(const pt_path_segment* paths, int64_t n, pt_shadeable_
     HitBuf hits{gp->d_hit_nt, gp->d_hit_mat, uvd0, uvd1};
     if (gp->gbvh_active)   // as both pipelines find the primitive winner in this mode
         launch_intersect_gbvh(1, dim3(nblocks((int)n)), pathbuf(0), hits, staged_count(0));
-    else if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
-        hipLaunchKernelGGL((k_intersect<true, true>), dim3(nblocks((int)n)), dim3(BLOCK), gp->bvh_lds, gp->stream, gp->sc,
-                           pathbuf(0), hits, staged_count(0));
-    else if (gp->has_bvh)
-        hipLaunchKernelGGL((k_intersect<true, false>), dim3(nblocks((int)n)), dim3(BLOCK), gp->bvh_lds, gp->stream, gp->sc,
-                           pathbuf(0), hits, staged_count(0));
     else
-        hipLaunchKernelGGL((k_intersect<false, false>), dim3(nblocks((int)n)), dim3(BLOCK), 0, gp->stream, gp->sc,
-                           pathbuf(0), hits, staged_count(0));
+        with_traversal([&](auto bvh, auto fast) {
+            hipLaunchKernelGGL((k_intersect<bvh.value, fast.value>), dim3(nblocks((int)n)), dim3(BLOCK), traversal_lds(),
+                               gp->stream, gp->sc, pathbuf(0), hits, staged_count(0));
+        });
     if (naive_tris)   // as the staged pipeline runs it
         hipLaunchKernelGGL(k_naive_mesh, dim3(nblocks((int)n)), dim3(BLOCK), 0, gp->stream, gp->sc,
                            (const DevTriHot*)gp->d_naive_hot, gp->sc.num_tris, pathbuf(0), hits.nt, hits.mat, hits.uvd0,

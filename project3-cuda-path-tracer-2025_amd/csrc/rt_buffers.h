@@ -173,20 +173,7 @@ void free_all() {
     gp->band_ready = nullptr;
     release_graph();
     free_pass_buffers();
-    for (auto& set : gp->d_gbuf)
-        for (float4*& p : set) dfree(p);
-    for (float4*& p : gp->d_dn_color) dfree(p);
-    for (float4*& p : gp->d_tp) dfree(p);
-    for (float4*& p : gp->d_chain_q) dfree(p);
-    dfree(gp->d_chain_followed);
-    dfree(gp->d_chain_cnt);
-    dfree(gp->d_rg_tab);
-    for (hipEvent_t& e : gp->dn_ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
-    for (hipEvent_t& e : gp->tp_ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
-    for (hipEvent_t& e : gp->rg_ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
+    gp->dn.release();
     void* ptrs[] = {gp->d_geoms, gp->d_cull, gp->d_mats, gp->d_nodes, gp->d_node_aux, gp->d_hot, gp->d_pairs, gp->d_quads, gp->d_hot4,
                     gp->d_leaf9, gp->d_cold, gp->d_naive_hot, gp->d_gbvh, gp->d_texels, gp->d_texinfo, gp->d_image, gp->d_ctl, gp->d_grid};
     for (void* p : ptrs)

@@ -2,8 +2,9 @@
 // inside its anonymous namespace; every rt_*.h is).
 //
 // Owns: the error string and the RC / HIPCHK return macros, dalloc / dfree, the per-context State
-// with the current-context pointer gp, the stream-ordered memset / memcpy, ctl_reset, need_init,
-// and launch() with the per-dispatch profiling records.
+// (with the DenoiseState it holds by value and that block's release) and the current-context pointer
+// gp, the stream-ordered memset / memcpy, ctl_reset, need_init, and launch() with the per-dispatch
+// profiling records.
 // Calls: HIP only.  Every other rt_*.h builds on this file; it knows none of them.
 using pth::Tuning;        // host/tuning.h: the knobs, read from the environment in read_tuning() alone
 using pth::read_tuning;
@@ -54,6 +55,59 @@ constexpr int MAXF = 256;                   // frames per pass, upper bound (slo
 // 1600^2 d12 1.38 / 1.27 / 1.23, bunny 0.397 / 0.388 / 0.391, cornell flat.  ~16 GB of path
 // buffers + 5.2 GB traversal queue at 1600^2, F = 32 (of 288 GB).
 constexpr int64_t AUTO_BATCH_PATHS = 84000000;
+
+// The denoiser's state, one block of the per-context State (rt_abi_denoise.h, _gbuffer_through.h,
+// _temporal.h, _regress.h).  pt_init allocates none of it: every buffer comes from the first call
+// that needs it, and release() frees whatever those calls left.
+struct DenoiseState {
+    // (pt/pt_denoise.h) feature planes + colour ping-pong, allocated by the first capture
+    // two sets of planes (the second allocated by the first pt_denoise_temporal): a capture never
+    // overwrites the set the temporal history refers to; gbuf_cur is the set the last capture wrote
+    float4* d_gbuf[2][3] = {};       // normal | t, position | hit, albedo | material
+    int gbuf_cur = 0;
+    float4* d_color[2] = {nullptr, nullptr};
+    bool gbuf_valid = false;         // captured with the current camera
+    hipEvent_t ev[PT_DENOISE_MAX_LEVELS + 3] = {};   // pt_debug_denoise_timing: capture 0-1, levels 2..
+    float capture_ms = 0.f, ms = 0.f, level_ms[PT_DENOISE_MAX_LEVELS] = {};
+    // through-capture (pt/pt_gbuffer_through.h), allocated by the first pt_gbuffer_capture_through
+    int gbuf_through = -1;           // max_specular of the captured buffer; -1: pt_gbuffer_capture's
+    float4* d_chain_q[2] = {nullptr, nullptr};   // ping-pong ray queues: pixels x (origin | pixel), then x (direction | t_sum)
+    int* d_chain_followed = nullptr; // delta surfaces followed, per pixel
+    int* d_chain_cnt = nullptr;      // a queue counter per round, CNT_PAD ints apart
+    // temporal stage (pt/pt_denoise_temporal.h), allocated by the first pt_denoise_temporal
+    float4* d_tp[4] = {};            // base colour | N_base, base moments, integrated colour | N, moments | variance
+    bool tp_history = false;         // the integrated planes hold a history (of set tp_hist_set, camera tp_cam)
+    bool tp_base_valid = false;      // the base planes belong to the current capture
+    bool tp_result = false;          // a call has filled the planes (pt_temporal_get)
+    int tp_hist_set = 0;
+    int tp_demod = 0;                // demodulate_albedo of the history
+    CamDev tp_cam{};
+    hipEvent_t tp_ev[4] = {};        // pt_debug_denoise_timing: reprojection, integration, levels
+    float tp_ms[3] = {};
+    // feature regression (pt/pt_denoise_regress.h), allocated by the first pt_denoise_regress
+    float* d_rg_tab = nullptr;       // the block table, RG_REC floats per block
+    bool rg_result = false;          // a call has filled the table (pt_regress_get)
+    hipEvent_t rg_ev[3] = {};        // pt_debug_denoise_timing: fit, apply
+    float rg_ms[2] = {};
+
+    void release() {
+        for (auto& set : d_gbuf)
+            for (float4*& p : set) dfree(p);
+        for (float4*& p : d_color) dfree(p);
+        for (float4*& p : d_chain_q) dfree(p);
+        dfree(d_chain_followed);
+        dfree(d_chain_cnt);
+        for (float4*& p : d_tp) dfree(p);
+        dfree(d_rg_tab);
+        auto destroy = [](auto& events) {
+            for (hipEvent_t& e : events)
+                if (e) (void)hipEventDestroy(e), e = nullptr;
+        };
+        destroy(ev);
+        destroy(tp_ev);
+        destroy(rg_ev);
+    }
+};
 
 struct State {
     bool inited = false;
@@ -143,35 +197,7 @@ struct State {
     int spec_dev_iter = 0;                // d_ctl_spec->iter after the speculative frames queued so far
     int key_bits = 1;
     bool multi = false;              // a shard context of a multi-device pt_init
-    // denoiser (pt/pt_denoise.h): feature planes + colour ping-pong, allocated by the first capture
-    // two sets of planes (the second allocated by the first pt_denoise_temporal): a capture never
-    // overwrites the set the temporal history refers to; gbuf_cur is the set the last capture wrote
-    float4* d_gbuf[2][3] = {};       // normal | t, position | hit, albedo | material
-    int gbuf_cur = 0;
-    float4* d_dn_color[2] = {nullptr, nullptr};
-    bool gbuf_valid = false;         // captured with the current camera
-    hipEvent_t dn_ev[PT_DENOISE_MAX_LEVELS + 3] = {};   // pt_debug_denoise_timing: capture 0-1, levels 2..
-    float dn_capture_ms = 0.f, dn_ms = 0.f, dn_level_ms[PT_DENOISE_MAX_LEVELS] = {};
-    // through-capture (pt/pt_gbuffer_through.h), allocated by the first pt_gbuffer_capture_through
-    int gbuf_through = -1;           // max_specular of the captured buffer; -1: pt_gbuffer_capture's
-    float4* d_chain_q[2] = {nullptr, nullptr};   // ping-pong ray queues: pixels x (origin | pixel), then x (direction | t_sum)
-    int* d_chain_followed = nullptr; // delta surfaces followed, per pixel
-    int* d_chain_cnt = nullptr;      // a queue counter per round, CNT_PAD ints apart
-    // temporal stage (pt/pt_denoise_temporal.h), allocated by the first pt_denoise_temporal
-    float4* d_tp[4] = {};            // base colour | N_base, base moments, integrated colour | N, moments | variance
-    bool tp_history = false;         // the integrated planes hold a history (of set tp_hist_set, camera tp_cam)
-    bool tp_base_valid = false;      // the base planes belong to the current capture
-    bool tp_result = false;          // a call has filled the planes (pt_temporal_get)
-    int tp_hist_set = 0;
-    int tp_demod = 0;                // demodulate_albedo of the history
-    CamDev tp_cam{};
-    hipEvent_t tp_ev[4] = {};        // pt_debug_denoise_timing: reprojection, integration, levels
-    float tp_ms[3] = {};
-    // feature regression (pt/pt_denoise_regress.h), allocated by the first pt_denoise_regress
-    float* d_rg_tab = nullptr;       // the block table, RG_REC floats per block
-    bool rg_result = false;          // a call has filled the table (pt_regress_get)
-    hipEvent_t rg_ev[3] = {};        // pt_debug_denoise_timing: fit, apply
-    float rg_ms[2] = {};
+    DenoiseState dn;                 // the denoiser's planes, flags and timings (above)
 };
 State g_primary;                 // the process's context (shard 0 of a multi-device context)
 State* gp = &g_primary;          // the context the host runtime works on now (see ShardScope)

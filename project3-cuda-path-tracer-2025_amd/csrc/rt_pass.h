@@ -1,7 +1,8 @@
 // rt_pass.h — one pass of the frame loop: which kernels it launches, and its captured graph.
 //
 // Owns: the table of fused kernel variants and the dispatch from a run-time variant to its
-// template instance (launch_bounce), effective_variant / head_fused / tail_from, the staged
+// template instance (launch_bounce), with_flag / with_traversal (a run-time flag, or the scene
+// traversal's pair of them, as template arguments), effective_variant / head_fused / tail_from, the staged
 // compaction's launch sequence, enqueue_pass (a pass's kernels on gp->stream), build_graph /
 // release_pass_graphs, pass_frames.
 // Calls: rt_core.h and the kernels.  It reads the buffers rt_buffers.h sizes but calls nothing
@@ -68,6 +69,17 @@ void with_flag(bool on, F&& f) {
     if (on) f(std::true_type{});
     else f(std::false_type{});
 }
+// f(has_bvh, fast): the scene traversal of this context's options as intersect_scene's two template
+// flags, fast = has_bvh && VAR_BVH_FAST.  Three instances, not four: no kernel is built for
+// <false, true>.  Every kernel that holds the traversal's stack in LDS is launched through this.
+template <class F>
+void with_traversal(F&& f) {
+    if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST)) f(std::true_type{}, std::true_type{});
+    else if (gp->has_bvh) f(std::true_type{}, std::false_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+// ... and the bytes of that stack
+size_t traversal_lds() { return gp->has_bvh ? gp->bvh_lds : 0; }
 
 // bytes of the geom hierarchy's LDS stack (c_gbvh.stack_entries x BLOCK ints on the device)
 size_t gbvh_stack_bytes() { return (size_t)gp->gbvh.stack_entries * BLOCK * sizeof(int); }
@@ -168,16 +180,10 @@ void launch_bounce(bool first, bool bvh, int var, dim3 grid, PathBuf in, PathBuf
 
 // the staged intersection stage through the geom hierarchy (k_intersect's three forms)
 void launch_intersect_gbvh(int kind, dim3 grid, PathBuf in, HitBuf hits, const int* n_in) {
-    const size_t lds = (gp->has_bvh ? gp->bvh_lds : 0) + gbvh_stack_bytes();
-    if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
-        launch(kind, k_intersect_gbvh<true, true>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
-               hits.uvd1, n_in);
-    else if (gp->has_bvh)
-        launch(kind, k_intersect_gbvh<true, false>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
-               hits.uvd1, n_in);
-    else
-        launch(kind, k_intersect_gbvh<false, false>, grid, dim3(BLOCK), lds, gp->sc, in, hits.nt, hits.mat, hits.uvd0,
-               hits.uvd1, n_in);
+    with_traversal([&](auto bvh, auto fast) {
+        launch(kind, k_intersect_gbvh<bvh.value, fast.value>, grid, dim3(BLOCK), traversal_lds() + gbvh_stack_bytes(),
+               gp->sc, in, hits.nt, hits.mat, hits.uvd0, hits.uvd1, n_in);
+    });
 }
 
 // stable compaction of the n_in paths of `pi` into `po` (three launches, see k_compact_*)
@@ -264,12 +270,11 @@ int enqueue_pass_body(int batch) {
         HitBuf hits{gp->d_hit_nt, gp->d_hit_mat, gp->d_hit_uvd0, gp->d_hit_uvd1};
         if (gp->gbvh_active)
             launch_intersect_gbvh(1, dim3(nb), pathbuf(cur), hits, n_in);
-        else if (gp->has_bvh && (gp->opts.variant & VAR_BVH_FAST))
-            launch(1, k_intersect<true, true>, dim3(nb), dim3(BLOCK), gp->bvh_lds, gp->sc, pathbuf(cur), hits, n_in);
-        else if (gp->has_bvh)
-            launch(1, k_intersect<true, false>, dim3(nb), dim3(BLOCK), gp->bvh_lds, gp->sc, pathbuf(cur), hits, n_in);
         else
-            launch(1, k_intersect<false, false>, dim3(nb), dim3(BLOCK), 0, gp->sc, pathbuf(cur), hits, n_in);
+            with_traversal([&](auto bvh, auto fast) {
+                launch(1, k_intersect<bvh.value, fast.value>, dim3(nb), dim3(BLOCK), traversal_lds(), gp->sc,
+                       pathbuf(cur), hits, n_in);
+            });
         // NAIVE_MESH_LOADING: every triangle in array order against the records just written
         if (gp->naive && gp->sc.num_tris > 0)
             launch(7, k_naive_mesh, dim3(nb), dim3(BLOCK), 0, gp->sc, (const DevTriHot*)gp->d_naive_hot, gp->sc.num_tris,

@@ -191,6 +191,16 @@ def test_textured_albedo(tmp_path, ptamd):
 H5 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
 
 
+def c0_reference(image, samples, g, demod, f):
+    """c0 as every denoiser forms it, in dtype `f`: image / samples, divided by max(albedo, 1e-3) at
+    hit pixels where demodulated.  image (h, w, 3)."""
+    hit = g["position"][..., 3] > 0.5
+    alb = np.maximum(g["albedo_mat"][..., :3], np.float32(1e-3)).astype(f)
+    with np.errstate(all="ignore"):
+        c = image.astype(f) / f(samples)
+        return np.where(hit[..., None], c / alb, c) if demod else c
+
+
 def atrous_reference(image, samples, g, p, f):
     """include/pt/pt_denoise.h's definition, every operation in dtype `f`.  image (h, w, 3)."""
     h, w = image.shape[:2]
@@ -200,9 +210,7 @@ def atrous_reference(image, samples, g, p, f):
     alb = np.maximum(g["albedo_mat"][..., :3], np.float32(1e-3)).astype(f)
     sc, sn, sp = (f(np.float32(p[k])) for k in ("sigma_color", "sigma_normal", "sigma_position"))
     with np.errstate(all="ignore"):
-        c = image.astype(f) / f(samples)
-        if p["demodulate_albedo"]:
-            c = np.where(hit[..., None], c / alb, c)
+        c = c0_reference(image, samples, g, p["demodulate_albedo"], f)
         for l in range(p["levels"]):
             s = 1 << l
             scl = sc * f(2.0 ** -l)

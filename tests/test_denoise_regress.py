@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, scene_path
-from test_denoise import NAN_INTERIOR, _eq, _synthetic_image
+from test_denoise import NAN_INTERIOR, _eq, _synthetic_image, c0_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +38,7 @@ def regress_reference(image, g, emittance, ridge, demod, f):
     hit = g["position"][..., 3] > 0.5
     alb = np.maximum(g["albedo_mat"][..., :3], np.float32(1e-3)).astype(f)
     surface = hit & ~(emittance[np.maximum(g["albedo_mat"][..., 3].astype(int), 0)] > 0)
-    with np.errstate(all="ignore"):
-        c = image.astype(f) / f(SAMPLES)
-        if demod:
-            c = np.where(hit[..., None], c / alb, c)
+    c = c0_reference(image, SAMPLES, g, demod, f)
     fin = np.isfinite(c).all(-1)
     sample = surface & fin
     nby, nbx = -(-h // 16) + 1, -(-w // 16) + 1

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, scene_path
-from test_denoise import H5, _synthetic_image
+from test_denoise import H5, _synthetic_image, c0_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +39,6 @@ def _camera(sc, move):
 
 _dot = lambda a, b: (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 _luma = lambda c, f: _dot(c, np.float32([0.2126, 0.7152, 0.0722]).astype(f))
-
-def _c0(img, g, demod, f):
-    hit = g["position"][..., 3] > 0.5
-    c = img.astype(f) / f(SAMPLES)
-    if demod:
-        c = np.where(hit[..., None], c / np.maximum(g["albedo_mat"][..., :3], np.float32(1e-3)).astype(f), c)
-    return c
 
 def reproject(hist, gh, cam, g, tp, f):
     """stage 1 -> (base colour | N_base, base moments, the discrete decisions per pixel)"""
@@ -85,7 +78,7 @@ def integrate(img, g, bcol, bmom, demod, var_hist_min, f):
     """stage 2 -> (colour | N, (mu1, mu2, variance))"""
     h, w = img.shape[:2]
     with np.errstate(all="ignore"):
-        c0 = _c0(img, g, demod, f)
+        c0 = c0_reference(img, SAMPLES, g, demod, f)
         fin = np.isfinite(c0).all(-1)
         c0 = np.where(fin[..., None], c0, f(0))
         L = _luma(c0, f)
@@ -206,7 +199,7 @@ def test_state_machine(ptamd):
     plain = tr.denoise(SAMPLES)
     first = tr.denoise_temporal(SAMPLES)
     pl = tr.temporal_planes()
-    c0 = _c0(img, g, 1, np.float32)
+    c0 = c0_reference(img, SAMPLES, g, 1, np.float32)
     fin = np.isfinite(c0).all(-1)
     assert np.array_equal(pl["color"][fin][:, :3], c0[fin]) and (pl["color"][fin][:, 3] == SAMPLES).all()
     assert (pl["color"][~fin] == 0).all() and (pl["base_color"] == 0).all()           # without history
