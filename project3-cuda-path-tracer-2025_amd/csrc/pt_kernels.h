@@ -629,15 +629,151 @@ PT_DEV bool trav_inner4(const SceneDev& sc, TravState& st, int* stack, int& n_no
     return true;
 }
 
+// ---- the 8-wide quantised layout (pt/pt_bvh_wide.h; records: DevWide8 / DevLeaf8 in pt_records.h) ----
+// Its buffers reach the two traversal kernels through c_wide8, not through SceneDev: the existing
+// kernels' arguments, and with them their code objects, stay what they were (as c_gbvh).
+//
+// Why it stays exact.  The argument for any hierarchy above the reference's leaves needs
+// inner boxes that contain their leaves' boxes and the reference's exact box decision at the leaf.
+// The host verifies, with decode8's own float expression, that every decoded child box contains the
+// child's true box, so it contains every leaf box below.  aabbIntersectionTest is monotone in the
+// bounds: a decoded box passes whenever a leaf box below it passes, so no leaf the reference visits
+// is lost -- only extra visits.  The entry distance of a containing box is no larger (the slab
+// products are monotone in the bounds, rounding included), so cull_threshold_packed from it is no
+// larger than the certified one: a cull can only be lost, never gained.  A quantised box can no
+// longer decide a leaf, so trav_leaf8 runs the exact decision on the leaf's own float box (what the
+// parent's record holds in the other layouts) and applies the certified cull on it before it
+// touches a triangle.  Ties go to the smaller hot4 slot, so the visiting order is free.
+struct Wide8Dev {
+    const uint32_t* rec;    // DevWide8 records as 32 dwords each; record 0 is the root's
+    const float4* leaf;     // DevLeaf8 records as 12 float4 each
+    int num;                // records; a ref >= num names the leaf ref - num
+};
+__constant__ Wide8Dev c_wide8;
+
+PT_DEV float decode8(float origin, float scale, uint32_t w, int k) {
+    return __builtin_fmaf((float)((w >> (8 * k)) & 0xffu), scale, origin);   // v_cvt_f32_ubyte<k>; the product is exact
+}
+// the certified decision on one box for this ray: the wave's fast form where it applies
+PT_DEV bool trav_box(const TravState& st, float4 lo, float4 hi, float& e) {
+    if (st.wfast) {   // wave-uniform
+        bool amb;
+        bool p = aabb_fast(lo, hi, st.ro, st.rr, e, amb);
+        if (amb) p = aabb_test(lo, hi, st.ro, st.rd);   // rare: the reference decides
+        return p;
+    }
+    return aabb_decide(lo, hi, st.ro, st.rd, st.rr, st.exact, e);
+}
+// Expand record st.cur.  Register budget: eight keys, thresholds and refs at once do not fit the
+// traversal kernels' 72 VGPRs, so the children are handled as two groups of four (one loop body,
+// run twice): per group 3 + 3 dwords of cell indices (four children per dword), 4 refs, 4 cull
+// constants; the group is ordered by entry with trav_inner4's network.  The nearest child of both
+// groups continues; each group's other passing children are pushed farthest first, and the loser
+// of the two groups' nearest is pushed last (it pops first).  The stack is then ordered within a
+// group only -- the order of visits never changes a result.
+template <bool COUNT = false>
+PT_DEV bool trav_inner8(const SceneDev& sc, TravState& st, int* stack, int& n_nodes) {
+    const float t_best = st.t_hit;
+    if (COUNT) n_nodes++;
+    const uint32_t* R = c_wide8.rec + 32 * (size_t)st.cur;
+    const int S = sc.ref_shift;
+    float bkey = __builtin_inff(), bT = 0.f;
+    int bref = -1;
+#pragma unroll 1
+    for (int g = 1; g >= 0; --g) {
+        const uint4 hd = *reinterpret_cast<const uint4*>(R);   // origin | exponents (re-read: same line, fewer live registers)
+        const float ox = __uint_as_float(hd.x), oy = __uint_as_float(hd.y), oz = __uint_as_float(hd.z);
+        const float sx = __uint_as_float((hd.w & 0xffu) << 23), sy = __uint_as_float((hd.w & 0xff00u) << 15),
+                    sz = __uint_as_float((hd.w & 0xff0000u) << 7);
+        const uint32_t lx = R[4 + g], ly = R[6 + g], lz = R[8 + g];
+        const uint32_t hx = R[10 + g], hy = R[12 + g], hz = R[14 + g];
+        const uint4 rf = *reinterpret_cast<const uint4*>(R + 16 + 4 * g);
+        const uint4 cl = *reinterpret_cast<const uint4*>(R + 24 + 4 * g);
+        float key[4], T[4];
+        int ref[4] = {(int)rf.x, (int)rf.y, (int)rf.z, (int)rf.w};
+        const uint32_t cu[4] = {cl.x, cl.y, cl.z, cl.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float4 lo = make_float4(decode8(ox, sx, lx, i), decode8(oy, sy, ly, i), decode8(oz, sz, lz, i), 0.f);
+            const float4 hi = make_float4(decode8(ox, sx, hx, i), decode8(oy, sy, hy, i), decode8(oz, sz, hz, i), 0.f);
+            float e = 0.f;
+            bool p = trav_box(st, lo, hi, e);
+            T[i] = cull_threshold_packed(e, __uint_as_float(cu[i]));
+            p = p && ref[i] >= 0 && !(t_best < T[i]);
+            key[i] = p ? e : __builtin_inff();
+        }
+        auto cx = [&](int a, int b) {
+            if (key[b] < key[a]) {
+                float tk = key[a]; key[a] = key[b]; key[b] = tk;
+                float tt = T[a]; T[a] = T[b]; T[b] = tt;
+                int tr = ref[a]; ref[a] = ref[b]; ref[b] = tr;
+            }
+        };
+        cx(0, 1); cx(2, 3); cx(0, 2); cx(1, 3); cx(1, 2);
+        if (key[0] < bkey) {   // the group's nearest against the nearest so far: the loser is pushed last
+            float tk = key[0]; key[0] = bkey; bkey = tk;
+            float tt = T[0]; T[0] = bT; bT = tt;
+            int tr = ref[0]; ref[0] = bref; bref = tr;
+        }
+#pragma unroll
+        for (int i = 3; i >= 1; --i)
+            if (key[i] < __builtin_inff()) trav_push(sc, st, stack, pack_ref(ref[i], T[i], S));
+        if (key[0] < __builtin_inff()) trav_push(sc, st, stack, pack_ref(ref[0], T[0], S));
+    }
+    if (!(bkey < __builtin_inff())) return false;    // no child passes: the caller pops
+    st.cur = bref;
+    st.curT = bT;
+    return true;
+}
+// leaf `leaf` of the 8-wide layout: the exact decision and the certified cull on the leaf's own box
+// (the decoded box that led here only contains it), then trav_leaf's four slots
+template <bool COUNT = false>
+PT_DEV void trav_leaf8(const SceneDev& sc, TravState& st, int leaf, int& n_nodes, int& n_tris) {
+    const v4f* L = reinterpret_cast<const v4f*>(c_wide8.leaf) + 12 * (size_t)leaf;
+    const v4f b0 = L[0], b1 = L[1];
+    if (COUNT) n_nodes++;
+    float e = 0.f;
+    const bool p = trav_box(st, make_float4(b0[0], b0[1], b0[2], 0.f), make_float4(b1[0], b1[1], b1[2], 0.f), e);
+    if (!p || st.t_hit < cull_threshold_packed(e, b0[3])) return;
+    const int base = 4 * leaf;
+    if (COUNT) {
+        n_tris += __float_as_int(b1[3]);
+        sec_add_lanes(SEC_N_LEAVES, 1);
+    }
+    v4f c[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c[k] = L[2 + k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f3 v0 = mk(c[0][i], c[1][i], c[2][i]);
+        const f3 e1 = mk(c[3][i], c[4][i], c[5][i]);
+        const f3 e2 = mk(c[6][i], c[7][i], c[8][i]);
+        float t, u, v;
+        if (tri_test_e(st.ro, st.rd, v0, e1, e2, t, u, v) && t > 0.0f &&
+            (t < st.t_hit || (t == st.t_hit && base + i < st.btri))) {
+            st.t_hit = t;
+            st.bu = u;
+            st.bv = v;
+            st.btri = base + i;
+        }
+    }
+}
+
+// the record layout a traversal kernel walks
+enum : int { LAY_PAIR = 0, LAY_QUAD = 1, LAY_WIDE8 = 2 };
+
 // one node expansion or one leaf; st.cur < 0 afterwards: the ray is finished
-template <bool COUNT = false, bool QUAD = false>
+template <bool COUNT = false, int LAY = LAY_PAIR>
 PT_DEV void trav_step(const SceneDev& sc, TravState& st, int* stack, int& n_nodes, int& n_tris) {
-    const int P = QUAD ? sc.num_quads : sc.num_pairs;
+    const int P = LAY == LAY_WIDE8 ? c_wide8.num : LAY == LAY_QUAD ? sc.num_quads : sc.num_pairs;
     bool next = false;
     if (st.cur < P) {
-        next = QUAD ? trav_inner4<COUNT>(sc, st, stack, n_nodes) : trav_inner<COUNT>(sc, st, stack, n_nodes);
+        if constexpr (LAY == LAY_WIDE8) next = trav_inner8<COUNT>(sc, st, stack, n_nodes);
+        else if constexpr (LAY == LAY_QUAD) next = trav_inner4<COUNT>(sc, st, stack, n_nodes);
+        else next = trav_inner<COUNT>(sc, st, stack, n_nodes);
     } else {
-        trav_leaf<COUNT>(sc, st, st.cur - P, n_nodes, n_tris);
+        if constexpr (LAY == LAY_WIDE8) trav_leaf8<COUNT>(sc, st, st.cur - P, n_nodes, n_tris);
+        else trav_leaf<COUNT>(sc, st, st.cur - P, n_nodes, n_tris);
     }
     if (!next) trav_pop(sc, st, stack);
 }
@@ -677,7 +813,7 @@ PT_DEV void trav_resume(TravState& st, f3 ro, f3 rd, float4 hit, int node, int q
 // `defer` lanes of the wave are still traversing: those stop with st.cur >= 0 (wave steps with a
 // handful of lanes cost a wave slot each for a few lanes of work; k_bvh_tail_trav resumes them in
 // full waves).  Counters (COUNT) as bvh_intersect_pairs', the per-ray ones left to the caller.
-template <bool COUNT = false, bool QUAD = false>
+template <bool COUNT = false, int LAY = LAY_PAIR>
 PT_DEV void trav_run(const SceneDev& sc, TravState& st, int* stack, int defer, int& n_nodes, int& n_tris,
                      int hist = SEC_BVH_LANES_HIST) {
     while (st.cur >= 0) {
@@ -687,7 +823,7 @@ PT_DEV void trav_run(const SceneDev& sc, TravState& st, int* stack, int defer, i
             sec_add(SEC_N_BVH_WITERS, 1);
             sec_add(hist + (lanes - 1) / 4, 1);
         }
-        trav_step<COUNT, QUAD>(sc, st, stack, n_nodes, n_tris);
+        trav_step<COUNT, LAY>(sc, st, stack, n_nodes, n_tris);
     }
 }
 

@@ -639,7 +639,7 @@ PT_DEV bool tail_put(const TailBuf& t, int* ctr, int seg, int qs, const TravStat
     return true;
 }
 
-template <int VAR, bool QUAD>
+template <int VAR, int LAY>
 __global__ __launch_bounds__(BLOCK, BVH_WAVES) void k_bvh_bounce(SceneDev sc, QueueBuf q, TailBuf tail, int defer,
                                                                  PathBuf out, FrameCtl* ctl, float* __restrict__ image,
                                                                  int bounce, int seg_stride) {
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(BLOCK, BVH_WAVES) void k_bvh_bounce(SceneDev sc, Qu
         if (CNT) sec_add_lanes(SEC_N_ROOT_CULLED, st.cur < 0 ? 1 : 0);
         // handed over: the wave's last few traversals go on 64 to a wave (no room: finish here)
         for (int d = defer;; d = 0) {
-            trav_run<CNT, QUAD>(sc, st, s_stack + tid, d, n_nodes, n_tris);
+            trav_run<CNT, LAY>(sc, st, s_stack + tid, d, n_nodes, n_tris);
             if (st.cur < 0) break;
             if (tail_put(tail, &ctl->qcnt[bounce][seg][1], seg, qs, st, s_stack + tid)) {
                 handed = true;
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(BLOCK, BVH_WAVES) void k_bvh_bounce(SceneDev sc, Qu
 // refill), so a wave drains once, when its segment is done, instead of once per 64 rays.
 // Traversal only: a finished ray's result (t, u, v, triangle) replaces its saved hit, and
 // k_bvh_tail_shade shades the entries in full waves.  No barrier: waves leave on their own.
-template <int VAR, bool QUAD>
+template <int VAR, int LAY>
 __global__ __launch_bounds__(BLOCK, BVH_WAVES) void k_bvh_tail_trav(SceneDev sc, QueueBuf q, TailBuf t, FrameCtl* ctl,
                                                                     int bounce, int refill) {
     extern __shared__ float4 s_dyn[];
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(BLOCK, BVH_WAVES) void k_bvh_tail_trav(SceneDev sc,
                 sec_add(SEC_N_BVH_WITERS, 1);
                 sec_add(SEC_TAIL_LANES_HIST + (lanes - 1) / 4, 1);
             }
-            trav_step<CNT, QUAD>(sc, st, s_stack, n_nodes, n_tris);
+            trav_step<CNT, LAY>(sc, st, s_stack, n_nodes, n_tris);
             if (st.cur < 0) {
                 t.hit[e] = trav_saved_hit(st);
                 if (CNT) {

@@ -154,6 +154,41 @@ struct DevPair {
     float4 r_hi;   // right box max.xyz | right cull constants
 };
 
+// One node of the 8-wide quantised layout (pt/pt_bvh_wide.h; host/trav_tree.cpp builds it, trav_inner8
+// walks it): up to eight children in ONE 128-byte line.  Child i's box decodes, per axis a, to
+//   lo = origin[a] + float(qlo[a][i]) * 2^(exp[a] - 127),  hi = origin[a] + float(qhi[a][i]) * 2^(exp[a] - 127)
+// (exp is a float's biased exponent field, 1..254; the product is exact, so the sum is the only
+// rounding and an fma gives the same float).  The host verifies with this very expression that the
+// decoded box contains the child's true box.  ref: -1 no child, < num_wide8 a record, else leaf +
+// num_wide8; cull: the child's pack_cull constants (bits of the float DevPair carries in hi.w).
+struct DevWide8 {
+    float origin[3];
+    uint8_t exp[3];
+    uint8_t count;
+    uint8_t qlo[3][8];
+    uint8_t qhi[3][8];
+    int32_t ref[8];
+    uint32_t cull[8];
+};
+static_assert(sizeof(DevWide8) == 128, "DevWide8");
+static_assert(offsetof(DevWide8, qlo) == 16 && offsetof(DevWide8, qhi) == 40 && offsetof(DevWide8, ref) == 64 &&
+                  offsetof(DevWide8, cull) == 96, "DevWide8 layout (trav_inner8 reads it by dword)");
+
+// Leaf record of the 8-wide layout, 192 bytes: a quantised box cannot decide a leaf, so the leaf
+// carries its exact box (the one DevPair / the 4-wide records hold for it) and its cull constants,
+// then leaf9's nine float4.  192 = 1.5 lines: a record starts at 0 or 64 (mod 128) and touches
+// exactly two lines either way (leaf9's 144-byte records touch up to three); 256 bytes would touch
+// the same two lines and take a third more memory.
+struct DevLeaf8 {
+    float lo[3];
+    uint32_t cull;      // pack_cull bits
+    float hi[3];
+    int32_t count;      // triangles in use (1..4)
+    float4 tri[9];      // leaf9: v0.x v0.y v0.z e1.x .. e2.z, each over the 4 slots
+    float4 spare;
+};
+static_assert(sizeof(DevLeaf8) == 192, "DevLeaf8");
+
 // hot triangle record in leaf order (index k = node.start + i): 3 positions, 48 bytes
 struct DevTriHot {
     float4 a;   // v0.xyz, v1.x

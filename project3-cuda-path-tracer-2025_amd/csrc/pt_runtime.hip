@@ -45,6 +45,7 @@
 #include "pt/pt_gbuffer_through.h"
 #include "pt/pt_naive_mesh.h"
 #include "pt/pt_geom_bvh.h"
+#include "pt/pt_bvh_wide.h"
 #include "pt_kernels.h"
 #include "pt_denoise_kernels.h"
 #include "pt_gbuffer_through_kernels.h"
@@ -147,9 +148,44 @@ static bool gbvh_next() {
     return g_gbvh_next != 0;
 }
 
+// the 8-wide quantised layout (pt/pt_bvh_wide.h): what the next pt_init uses; g_wide_next < 0 until
+// first asked, then PT_BVH_WIDE from the environment or what pt_set_bvh_wide stored
+constexpr int WIDE_MIN_REFS = 65536;
+static int g_wide_next = -1, g_wide_min = WIDE_MIN_REFS;
+static bool wide_next() {
+    if (g_wide_next < 0) {
+        const char* e = getenv("PT_BVH_WIDE");
+        const long v = e ? strtol(e, nullptr, 10) : 0;
+        g_wide_next = v >= 1 ? 1 : 0;
+        g_wide_min = v > 1 ? (int)std::min<long>(v, 1 << 30) : WIDE_MIN_REFS;
+    }
+    return g_wide_next != 0;
+}
+
 extern "C" {
 
 int32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+int32_t pt_set_bvh_wide(int32_t enabled, int32_t min_refs) {
+    g_wide_next = enabled ? 1 : 0;
+    g_wide_min = min_refs > 0 ? min_refs : WIDE_MIN_REFS;
+    return PT_OK;
+}
+int32_t pt_get_bvh_wide(int32_t* next_enabled, int32_t* next_min, int32_t* active) {
+    const bool on = wide_next();
+    if (next_enabled) *next_enabled = on ? 1 : 0;
+    if (next_min) *next_min = g_wide_min;
+    if (active) *active = (g_primary.inited && g_primary.wide8_active) ? 1 : 0;
+    return PT_OK;
+}
+int32_t pt_debug_bvh_wide_info(int32_t* num_records, int32_t* height, int32_t* stack_entries, int32_t* leaf_bytes) {
+    const bool on = g_primary.inited && g_primary.wide8_active;
+    if (num_records) *num_records = on ? g_primary.wide8_records : 0;
+    if (height) *height = on ? g_primary.wide8_height : 0;
+    if (stack_entries) *stack_entries = on ? g_primary.wide8_stack : 0;
+    if (leaf_bytes) *leaf_bytes = on ? (int32_t)sizeof(DevLeaf8) : 0;
+    return PT_OK;
+}
 
 int32_t pt_set_geom_bvh(int32_t enabled, int32_t min_geoms) {
     g_gbvh_next = enabled ? 1 : 0;
@@ -332,6 +368,11 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     lp.geom_bvh_stack_budget =
         (int)((65536 - (o.material_sort && o.pipeline == PT_PIPELINE_FUSED ? mat_group_lds(true, false) : 0)) /
               (BLOCK * sizeof(int)));
+    // the 8-wide quantised records: one unsharded context outside the naive mode (and only where the
+    // split queue is live, below)
+    const bool wide_wanted = wide_next() && !naive && o.shard_mode == PT_SHARD_NONE && o.num_devices <= 1 &&
+                             o.pipeline == PT_PIPELINE_FUSED;
+    lp.bvh_wide_min = wide_wanted ? g_wide_min : 0;
     pth::SceneLayout L;
     {
         std::string err;
@@ -364,6 +405,12 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
         !(variant_compiled(effective_variant(true, o.variant)) && variant_compiled(effective_variant(false, o.variant))))
         gp->gbvh_active = false;
     if (gp->gbvh_active) gp->split = false;   // mesh rays are not split off: no traversal queue
+    // the 8-wide layout serves k_bvh_bounce / k_bvh_tail_trav only: without the split queue the
+    // tracer runs as without the mode
+    gp->wide8_active = gp->split && !L.wide8.empty();
+    gp->wide8_records = (int)L.wide8.size();
+    gp->wide8_height = L.wide8_height;
+    gp->wide8_stack = L.wide8_stack;
     if (o.pipeline == PT_PIPELINE_FUSED) {
         for (int first = 0; first < 2; ++first) {
             const int v = effective_variant(first != 0, o.variant);
@@ -404,7 +451,14 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     RC(to_device(&gp->d_pairs, L.pairs));
     RC(to_device(&gp->d_hot4, L.hot4));
     RC(to_device(&gp->d_leaf9, L.leaf9));
-    RC(to_device(&gp->d_quads, L.quads));
+    if (!gp->wide8_active) RC(to_device(&gp->d_quads, L.quads));   // the traversal kernels walk one layout
+    if (gp->wide8_active) {
+        RC(to_device(&gp->d_wide8, L.wide8));
+        RC(to_device(&gp->d_leaf8, L.leaf8));
+        const Wide8Dev wd{reinterpret_cast<const uint32_t*>(gp->d_wide8), reinterpret_cast<const float4*>(gp->d_leaf8),
+                          (int)L.wide8.size()};
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_wide8), &wd, sizeof(Wide8Dev)));
+    }
     RC(to_device(&gp->d_naive_hot, L.naive_hot));
     if (gp->gbvh_active) {
         RC(to_device(&gp->d_gbvh, L.geom_bvh.nodes));
@@ -463,9 +517,13 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     sc.pair_stack_depth = gp->pair_depth > 0 ? std::min(gp->pair_depth, gp->stack_depth) : gp->stack_depth;
     // the split kernels' LDS stack: all of it, or its first bvh_stack_lds entries and a spill row per
     // queue slot for the rest
-    sc.stack_lds = gp->split && gp->tune.bvh_stack_lds > 0 ? std::min(gp->tune.bvh_stack_lds, sc.pair_stack_depth)
-                                                           : sc.pair_stack_depth;
-    sc.spill_stride = sc.pair_stack_depth - sc.stack_lds;
+    // (8-wide layout: up to seven pushes per record, wide8_stack entries in all -- the traversal
+    // kernels' push bound, launch_bounce_t.  By default the LDS part stays what the pairs would take, so
+    // the kernels' occupancy is the same, and the rest goes to the spill rows.)
+    const int trav_depth = gp->wide8_active ? gp->wide8_stack : sc.pair_stack_depth;
+    sc.stack_lds = gp->split && gp->tune.bvh_stack_lds > 0 ? std::min(gp->tune.bvh_stack_lds, trav_depth)
+                                                           : std::min(trav_depth, sc.pair_stack_depth);
+    sc.spill_stride = trav_depth - sc.stack_lds;
     sc.spill = nullptr;   // allocated with the traversal queue (ensure_frames)
     sc.cam = to_camdev(s->camera);
     sc.shard = sh;

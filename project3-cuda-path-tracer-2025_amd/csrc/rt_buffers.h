@@ -175,7 +175,7 @@ void free_all() {
     free_pass_buffers();
     gp->dn.release();
     void* ptrs[] = {gp->d_geoms, gp->d_cull, gp->d_mats, gp->d_nodes, gp->d_node_aux, gp->d_hot, gp->d_pairs, gp->d_quads, gp->d_hot4,
-                    gp->d_leaf9, gp->d_cold, gp->d_naive_hot, gp->d_gbvh, gp->d_texels, gp->d_texinfo, gp->d_image, gp->d_ctl, gp->d_grid};
+                    gp->d_leaf9, gp->d_cold, gp->d_naive_hot, gp->d_gbvh, gp->d_wide8, gp->d_leaf8, gp->d_texels, gp->d_texinfo, gp->d_image, gp->d_ctl, gp->d_grid};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (gp->stream) (void)hipStreamDestroy(gp->stream);

@@ -145,6 +145,11 @@ struct State {
     DevGeomNode* d_gbvh = nullptr;
     GeomBvhDev gbvh{};
     bool gbvh_active = false;
+    // the 8-wide quantised layout (pt/pt_bvh_wide.h); wide8_active: the two traversal kernels walk it
+    DevWide8* d_wide8 = nullptr;
+    DevLeaf8* d_leaf8 = nullptr;
+    bool wide8_active = false;
+    int wide8_records = 0, wide8_height = 0, wide8_stack = 0;
     float4* d_path[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     float4* d_hit_nt = nullptr;
     int* d_hit_mat = nullptr;

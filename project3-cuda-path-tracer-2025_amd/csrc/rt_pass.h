@@ -69,6 +69,15 @@ void with_flag(bool on, F&& f) {
     if (on) f(std::true_type{});
     else f(std::false_type{});
 }
+// f(layout): the record layout the two traversal kernels walk in this context -- the 8-wide
+// quantised records (pt/pt_bvh_wide.h) when the mode is active, else the 4-wide ones when they
+// were uploaded, else the pairs
+template <class F>
+void with_layout(F&& f) {
+    if (gp->wide8_active) f(std::integral_constant<int, LAY_WIDE8>{});
+    else if (gp->sc.quads != nullptr) f(std::integral_constant<int, LAY_QUAD>{});
+    else f(std::integral_constant<int, LAY_PAIR>{});
+}
 // f(has_bvh, fast): the scene traversal of this context's options as intersect_scene's two template
 // flags, fast = has_bvh && VAR_BVH_FAST.  Three instances, not four: no kernel is built for
 // <false, true>.  Every kernel that holds the traversal's stack in LDS is launched through this.
@@ -114,15 +123,17 @@ void launch_bounce_t(dim3 grid, PathBuf in, PathBuf out, int b) {
         const size_t stack_bytes = (size_t)gp->sc.stack_lds * BLOCK * sizeof(int);
         // the handed-over stacks were sized for the pair tree of the allocation (ensure_frames)
         if (gp->tail_lanes > 0 && gp->sc.stack_lds > gp->tail_depth) gp->tail_lanes = 0;
-        const bool quads = gp->sc.quads != nullptr;   // the 4-wide layout (trees past the L2)
-        with_flag(quads, [&](auto quad) {
-            launch(200 + b, k_bvh_bounce<VAR, quad.value>, grid, dim3(BLOCK), stack_bytes + lds_pad, gp->sc, gp->queue,
+        // the 8-wide layout's push bound (wide8_stack entries) holds for these two kernels only
+        SceneDev tsc = gp->sc;
+        if (gp->wide8_active) tsc.pair_stack_depth = gp->wide8_stack;
+        with_layout([&](auto lay) {
+            launch(200 + b, k_bvh_bounce<VAR, lay.value>, grid, dim3(BLOCK), stack_bytes + lds_pad, tsc, gp->queue,
                    gp->tail, gp->tail_lanes, out, gp->d_ctl, gp->d_image, b, gp->seg_stride);
         });
         if (gp->tail_lanes > 0) {   // the handed-over rays: refilling waves, then their shading
-            with_flag(quads, [&](auto quad) {
-                launch(400 + b, k_bvh_tail_trav<VAR, quad.value>, dim3(NSEG * gp->tail_trav_blocks), dim3(BLOCK),
-                       stack_bytes, gp->sc, gp->queue, gp->tail, gp->d_ctl, b, gp->tail_refill);
+            with_layout([&](auto lay) {
+                launch(400 + b, k_bvh_tail_trav<VAR, lay.value>, dim3(NSEG * gp->tail_trav_blocks), dim3(BLOCK),
+                       stack_bytes, tsc, gp->queue, gp->tail, gp->d_ctl, b, gp->tail_refill);
             });
             const int per_seg = gp->tail_shade_blocks > 0 ? std::min(gp->tail_shade_blocks, nblocks(gp->tail.stride))
                                                           : nblocks(gp->tail.stride);

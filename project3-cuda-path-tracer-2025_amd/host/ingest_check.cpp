@@ -228,11 +228,28 @@ static bool parse_param(const std::string& kv, pth::LayoutParams& p) {
     else if (k == "sah_max_height") p.sah_max_height = x;
     else if (k == "geom_bvh_min") p.geom_bvh_min = x;
     else if (k == "geom_bvh_stack_budget") p.geom_bvh_stack_budget = x;
+    else if (k == "bvh_wide_min") p.bvh_wide_min = x;
     else return false;
     return true;
 }
 
-static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p, const char* gbvh_out = nullptr) {
+// the 8-wide layout as raw bytes: int32 {records, leaves, stack entries, height}, the DevWide8
+// records, the DevLeaf8 records, the leaves' hot4 slots (records = 0: the mode does not apply)
+static bool write_wide8(const pth::SceneLayout& l, const char* out) {
+    std::FILE* f = std::fopen(out, "wb");
+    if (!f) return false;
+    const int32_t hd[4] = {(int32_t)l.wide8.size(), (int32_t)l.leaf8.size(), l.wide8_stack, l.wide8_height};
+    bool ok = std::fwrite(hd, sizeof(hd), 1, f) == 1;
+    if (!l.wide8.empty()) {
+        ok = ok && std::fwrite(l.wide8.data(), sizeof(ptd::DevWide8), l.wide8.size(), f) == l.wide8.size();
+        ok = ok && std::fwrite(l.leaf8.data(), sizeof(ptd::DevLeaf8), l.leaf8.size(), f) == l.leaf8.size();
+        ok = ok && std::fwrite(l.hot4.data(), sizeof(ptd::DevTriHot), l.hot4.size(), f) == l.hot4.size();
+    }
+    return std::fclose(f) == 0 && ok;
+}
+
+static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p, const char* gbvh_out = nullptr,
+                        const char* wide_out = nullptr) {
     pth::SceneLayout l;
     std::string err;
     const int rc = pth::build_scene_layout(v, p, l, err);
@@ -268,6 +285,15 @@ static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p, cons
             std::printf("scalar geom_bvh_height %d\nscalar geom_bvh_stack %d\n", l.geom_bvh.height,
                         l.geom_bvh.stack_entries);
         }
+        if (!l.wide8.empty()) {   // only when the mode is on and applies
+            print_buf("wide8", l.wide8);
+            print_buf("leaf8", l.leaf8);
+            std::printf("scalar wide8_stack %d\nscalar wide8_height %d\n", l.wide8_stack, l.wide8_height);
+        }
+        if (wide_out && !write_wide8(l, wide_out)) {
+            std::fprintf(stderr, "cannot write %s\n", wide_out);
+            return 2;
+        }
         if (gbvh_out) {   // the node array as raw bytes (an empty file: no tree)
             std::FILE* f = std::fopen(gbvh_out, "wb");
             const size_t nn = l.geom_bvh.nodes.size();
@@ -285,13 +311,19 @@ static int print_layout(const pt_scene_view& v, const pth::LayoutParams& p, cons
 
 // `layout FILE.json [key=value ...]` (kind null) / `layout-mutate FILE.json KIND` /
 // `geom-bvh FILE.json [min=N] [out=PATH] [key=value ...]` (gbvh): the layout with the geom hierarchy on
-// (min: its threshold, default 1), the node array written to PATH
-static int check_layout(const char* path, const char* kind, int nkv, char** kv, bool gbvh = false) {
+// (min: its threshold, default 1), the node array written to PATH /
+// `wide8 FILE.json OUT [min=N] [key=value ...]` (wide_out): the layout with the 8-wide records on
+// (min: their threshold in refs, default 1), records, leaf records and scalars written to OUT
+static int check_layout(const char* path, const char* kind, int nkv, char** kv, bool gbvh = false,
+                        const char* wide_out = nullptr) {
     pth::LayoutParams p;
     std::string gbvh_out;
     if (gbvh) p.geom_bvh_min = 1;
+    if (wide_out) p.bvh_wide_min = 1;
     for (int i = 0; i < nkv; ++i)
-        if (gbvh && std::strncmp(kv[i], "out=", 4) == 0) {
+        if (wide_out && std::strncmp(kv[i], "min=", 4) == 0) {
+            p.bvh_wide_min = std::max(1, std::atoi(kv[i] + 4));
+        } else if (gbvh && std::strncmp(kv[i], "out=", 4) == 0) {
             gbvh_out = kv[i] + 4;
         } else if (gbvh && std::strncmp(kv[i], "min=", 4) == 0) {
             p.geom_bvh_min = std::max(1, std::atoi(kv[i] + 4));
@@ -318,7 +350,7 @@ static int check_layout(const char* path, const char* kind, int nkv, char** kv, 
         v.bvh_nodes = nodes.data();
         v.tri_indices = idx.data();
     }
-    if (ret == 0 && print_layout(v, p, gbvh_out.empty() ? nullptr : gbvh_out.c_str()) == 2) ret = 2;
+    if (ret == 0 && print_layout(v, p, gbvh_out.empty() ? nullptr : gbvh_out.c_str(), wide_out) == 2) ret = 2;
     pt_scene_free(f);
     return ret;
 }
@@ -349,13 +381,14 @@ static int save_png(const char* out, int w, int h) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s scene|png FILE... | savepng OUT W H | layout FILE [key=value ...] | "
-                             "layout-mutate FILE KIND | geom-bvh FILE [min=N] [out=PATH]\n", argv[0]);
+                             "layout-mutate FILE KIND | geom-bvh FILE [min=N] [out=PATH] | wide8 FILE OUT [min=N]\n", argv[0]);
         return 2;
     }
     const std::string mode = argv[1];
     if (mode == "savepng" && argc == 5) return save_png(argv[2], std::atoi(argv[3]), std::atoi(argv[4])) == 0 ? 0 : 1;
     if (mode == "layout") return check_layout(argv[2], nullptr, argc - 3, argv + 3);
     if (mode == "geom-bvh") return check_layout(argv[2], nullptr, argc - 3, argv + 3, true);
+    if (mode == "wide8" && argc >= 4) return check_layout(argv[2], nullptr, argc - 4, argv + 4, false, argv[3]);
     if (mode == "layout-mutate" && argc == 4) return check_layout(argv[2], argv[3], 0, nullptr);
     for (int i = 2; i < argc; ++i) {
         std::printf("%s: ", argv[i]);

@@ -9,8 +9,9 @@
 //             [--devices N | --devices K0,K1,...] [--combine peer|rccl]
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
 //             [--denoise [LEVELS] [--denoise-through K]] [--denoise-temporal [LEVELS]] [--naive-mesh]
-//             [--denoise-regress [RIDGE]] [--geom-bvh [MIN]]
+//             [--denoise-regress [RIDGE]] [--geom-bvh [MIN]] [--bvh-wide [MIN]]
 //
+// --bvh-wide walks mesh trees of at least MIN refs as 8-wide quantised records (include/pt/pt_bvh_wide.h)
 // --geom-bvh traces the cubes and spheres through a 4-wide hierarchy over them (include/pt/pt_geom_bvh.h)
 // in scenes of at least MIN geoms (default 65): same image, for scenes of many primitives.
 // --naive-mesh renders in the reference's NAIVE_MESH_LOADING mode (include/pt/pt_naive_mesh.h): every
@@ -51,6 +52,7 @@
 
 #include "image_io.h"
 #include "pathtrace.h"
+#include "pt/pt_bvh_wide.h"
 #include "pt/pt_denoise.h"
 #include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
@@ -184,12 +186,14 @@ int main(int argc, char** argv) {
                     "[--pipeline fused|staged] [--sort] [--no-compaction] [--no-bvh] [--device K] [--gpu-bvh] "
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
                     "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS] [--denoise-through K]] "
-                    "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]] [--geom-bvh [MIN]]\n", argv[0]);
+                    "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]] [--geom-bvh [MIN]] "
+                    "[--bvh-wide [MIN]]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
     bool gpu_bvh = false, naive_mesh = false;
     int geom_bvh_min = -1;    // -1: no --geom-bvh; 0: its default threshold
+    int bvh_wide_min = -1;    // the same for --bvh-wide
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
     int temporal_levels = 0;  // 0: no --denoise-temporal
@@ -214,17 +218,18 @@ int main(int argc, char** argv) {
         else if (a == "--device") opts.device = std::atoi(next());
         else if (a == "--gpu-bvh") gpu_bvh = true;
         else if (a == "--naive-mesh") naive_mesh = true;
-        else if (a == "--geom-bvh") {   // the threshold is optional, like --denoise's level count
-            geom_bvh_min = 0;
+        else if (a == "--geom-bvh" || a == "--bvh-wide") {   // the threshold is optional, like --denoise's level count
+            int& min = a == "--geom-bvh" ? geom_bvh_min : bvh_wide_min;
+            min = 0;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
                 const char* v = argv[++i];
                 char* end = nullptr;
                 const long n = std::strtol(v, &end, 10);
                 if (end == v || *end != '\0' || n < 1 || n > (1 << 30)) {
-                    std::fprintf(stderr, "usage: --geom-bvh [MIN], MIN an integer >= 1, got '%s'\n", v);
+                    std::fprintf(stderr, "usage: %s [MIN], MIN an integer >= 1, got '%s'\n", a.c_str(), v);
                     return 2;
                 }
-                geom_bvh_min = (int)n;
+                min = (int)n;
             }
         }
         else if (a == "--devices") {   // every frame split into pixel shards over these GPUs
@@ -296,6 +301,7 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (geom_bvh_min >= 0) pathtraceSetGeomBvh(true, geom_bvh_min);
+    if (bvh_wide_min >= 0) pt_set_bvh_wide(1, bvh_wide_min);
     if (naive_mesh) {   // the mode runs on the staged pipeline
         pathtraceSetNaiveMesh(true);
         opts.pipeline = PT_PIPELINE_STAGED;

@@ -667,6 +667,60 @@ int fill_quads(const std::vector<TravInner>& tt, int bfs_levels, const CullPacke
     return Q > 0 ? qneed + 1 : 0;
 }
 
+// The 8-wide quantised form of the SAH hierarchy (DevWide8 / DevLeaf8, pt/pt_bvh_wide.h).  Leaves
+// `wide8` / `leaf8` empty when a record cannot be encoded or the traversal could need more stack
+// entries than the hand-over saves (7 bits of depth, as fill_quads).  `leaf9` / `hot4` are the
+// leaf records already built; the leaves' exact boxes and cull sizes come from the tree's leaf children.
+void fill_wide8(const std::vector<TravInner>& tt, int bfs_levels, const CullPacker& pack_cull,
+                const std::vector<DevTriHot>& hot4, const std::vector<float4>& leaf9, SceneLayout& out) {
+    std::vector<Wide8Record> wr;
+    int need = 0;
+    build_wide8_records(tt, std::max(0, bfs_levels / 3), wr, need);
+    if (wr.empty() || need + 1 > 96) return;
+    const int W = (int)wr.size();
+    const size_t L = leaf9.size() / 9;
+    auto bits = [](float f) {
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        return u;
+    };
+    std::vector<DevWide8> rec(W);
+    std::vector<DevLeaf8> leaf(L);
+    std::vector<int> level(W, 1);   // records are numbered parent before child in both orders
+    int height = 1;
+    for (int w = 0; w < W; ++w) {
+        DevWide8& R = rec[w];
+        memset(&R, 0, sizeof(R));
+        if (!quantise_wide8(wr[w], R.origin, R.exp, R.qlo, R.qhi)) return;
+        R.count = (uint8_t)wr[w].n;
+        for (int i = 0; i < 8; ++i) {
+            R.ref[i] = -1;
+            if (i >= wr[w].n) continue;
+            const TravChild& c = wr[w].c[i];
+            R.ref[i] = c.leaf ? W + c.ref : c.ref;
+            R.cull[i] = bits(pack_cull(c.s));
+            if (c.leaf) {
+                DevLeaf8& lf = leaf[c.ref];
+                for (int a = 0; a < 3; ++a) {
+                    lf.lo[a] = c.lo[a];
+                    lf.hi[a] = c.hi[a];
+                }
+                lf.cull = R.cull[i];
+                lf.count = (int32_t)bits(hot4[4 * (size_t)c.ref].c.z);
+                for (int m = 0; m < 9; ++m) lf.tri[m] = leaf9[9 * (size_t)c.ref + m];
+                lf.spare = make_float4(0.f, 0.f, 0.f, 0.f);
+                height = std::max(height, level[w] + 1);
+            } else {
+                level[c.ref] = level[w] + 1;
+            }
+        }
+    }
+    out.wide8.swap(rec);
+    out.leaf8.swap(leaf);
+    out.wide8_stack = need + 1;
+    out.wide8_height = height;
+}
+
 // ---- leaf records: hot4 (4 triangle slots per leaf, slot 0's c.z = count) and trav_step's leaf9:
 // component k of the 4 slots in one float4, positions as v0 and the float edges v1 - v0, v2 - v0
 // (tri_test's own first rounding) ----
@@ -732,6 +786,12 @@ void build_pair_layout(const pt_scene_view& s, const LayoutParams& p, bool neste
         out.pair_depth = rt.height + 1;
     }
     fill_leaf_records(s, rt, out.hot, out.hot4, out.leaf9);
+    if (sah && p.bvh_wide_min > 0 && (int64_t)P + L >= p.bvh_wide_min) {
+        fill_wide8(tt, p.bvh_bfs_levels, pack_cull, out.hot4, out.leaf9, out);
+        if (p.bvh_tree_info)
+            fprintf(stderr, "pt_init: 8-wide records %d (pairs %d), height %d, stack %d entries\n", (int)out.wide8.size(), P,
+                    out.wide8_height, out.wide8_stack);
+    }
     out.root_ref = sah ? 0 : rt.ref(0);
     out.root_lo = make_float4(out.nodes[0].lo.x, out.nodes[0].lo.y, out.nodes[0].lo.z, 0.f);
     out.root_hi = make_float4(out.nodes[0].hi.x, out.nodes[0].hi.y, out.nodes[0].hi.z, out.node_aux[0].y);

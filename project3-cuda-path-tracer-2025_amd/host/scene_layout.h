@@ -35,6 +35,9 @@ struct LayoutParams {
     // geom_bvh_stack_budget LDS entries per lane (resolved by the runtime from its kernels' LDS)
     int geom_bvh_min = 0;
     int geom_bvh_stack_budget = 64;
+    // the 8-wide quantised records (pt/pt_bvh_wide.h): built beside the pairs for SAH trees of at
+    // least bvh_wide_min refs (0: the mode is off)
+    int bvh_wide_min = 0;
 };
 
 struct SceneLayout {
@@ -61,6 +64,12 @@ struct SceneLayout {
     int stack_depth = 0;                    // LDS stack entries per lane, all traversals
     int pair_depth = 0;                     // entries the pair traversal needs: height of its hierarchy + 1
     int quad_stack = 0;                     // stack entries the 4-wide traversal can need
+    // the 8-wide quantised layout (both empty: off, or the tree cannot be encoded / is too small /
+    // needs a deeper stack than the hand-over can save)
+    std::vector<ptd::DevWide8> wide8;
+    std::vector<ptd::DevLeaf8> leaf8;
+    int wide8_stack = 0;                    // stack entries its traversal can need
+    int wide8_height = 0;                   // record levels plus the leaf level
     int root_ref = 0, pair_count = 0, ref_shift = 16;
     float4 root_lo{}, root_hi{};            // root box (hi.w: root cull size)
     double cull_extent = 1.0;

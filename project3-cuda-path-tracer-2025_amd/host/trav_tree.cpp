@@ -290,4 +290,127 @@ void build_quad_records(const std::vector<TravInner>& tt, int bfs_levels, std::v
     stack_need = need[0];
 }
 
+void build_wide8_records(const std::vector<TravInner>& tt, int bfs_levels, std::vector<Wide8Record>& out,
+                         int& stack_need) {
+    out.clear();
+    stack_need = 0;
+    if (tt.empty()) return;
+    const int P = (int)tt.size();
+    auto area = [](const TravChild& c) {
+        const double x = (double)c.hi[0] - c.lo[0], y = (double)c.hi[1] - c.lo[1], z = (double)c.hi[2] - c.lo[2];
+        return x * y + y * z + z * x;
+    };
+    // the children of the record headed by binary node n (refs still the binary tree's)
+    auto kids = [&](int n, TravChild* k8) {
+        int k = 2;
+        k8[0] = tt[n].c[0];
+        k8[1] = tt[n].c[1];
+        while (k < 8) {
+            int best = -1;
+            double ba = -1.0;
+            for (int i = 0; i < k; ++i)
+                if (!k8[i].leaf && area(k8[i]) > ba) {
+                    ba = area(k8[i]);
+                    best = i;
+                }
+            if (best < 0) break;
+            const int r = k8[best].ref;
+            k8[best] = tt[r].c[0];   // in place, then the sibling at the end
+            k8[k++] = tt[r].c[1];
+        }
+        return k;
+    };
+    std::vector<int> head{0}, depth{0}, wid(P, -1);
+    wid[0] = 0;
+    for (size_t h = 0; h < head.size(); ++h) {
+        TravChild k8[8];
+        const int nk = kids(head[h], k8);
+        for (int i = 0; i < nk; ++i)
+            if (!k8[i].leaf) {
+                wid[k8[i].ref] = (int)head.size();
+                head.push_back(k8[i].ref);
+                depth.push_back(depth[h] + 1);
+            }
+    }
+    const int W = (int)head.size();
+    const int lev = std::max(0, bfs_levels);
+    std::vector<int> order, num(W, -1), roots;
+    for (int h = 0; h < W; ++h) {
+        if (depth[h] < lev) order.push_back(h);
+        else if (depth[h] == lev) roots.push_back(h);
+    }
+    for (int r : roots) {   // each subtree below the breadth-first levels in preorder
+        std::vector<int> st{r};
+        while (!st.empty()) {
+            const int h = st.back();
+            st.pop_back();
+            order.push_back(h);
+            TravChild k8[8];
+            const int nk = kids(head[h], k8);
+            for (int i = nk - 1; i >= 0; --i)
+                if (!k8[i].leaf) st.push_back(wid[k8[i].ref]);
+        }
+    }
+    for (int i = 0; i < (int)order.size(); ++i) num[order[i]] = i;
+    out.assign(W, Wide8Record{});
+    std::vector<int> need(W, 0);
+    for (int h = W - 1; h >= 0; --h) {   // a record's children come after it breadth-first
+        Wide8Record& R = out[num[h]];
+        R.n = kids(head[h], R.c);
+        int deeper = 0;
+        for (int i = 0; i < R.n; ++i)
+            if (!R.c[i].leaf) {
+                const int ch = wid[R.c[i].ref];
+                deeper = std::max(deeper, need[ch]);
+                R.c[i].ref = num[ch];
+            }
+        need[h] = (R.n - 1) + deeper;
+    }
+    stack_need = need[0];
+}
+
+bool quantise_wide8(const Wide8Record& r, float origin[3], unsigned char exp[3], unsigned char qlo[3][8],
+                    unsigned char qhi[3][8]) {
+    for (int a = 0; a < 3; ++a) {
+        float lo = r.c[0].lo[a], hi = r.c[0].hi[a];
+        for (int i = 0; i < r.n; ++i) {
+            if (!std::isfinite(r.c[i].lo[a]) || !std::isfinite(r.c[i].hi[a]) || r.c[i].lo[a] > r.c[i].hi[a]) return false;
+            lo = std::min(lo, r.c[i].lo[a]);
+            hi = std::max(hi, r.c[i].hi[a]);
+        }
+        origin[a] = lo;
+        // the smallest cell 2^(e - 127) whose 255 cells reach hi, then larger ones until every child encodes
+        int e = 1;
+        if (hi > lo) {
+            int x;
+            std::frexp(((double)hi - (double)lo) / 255.0, &x);   // extent / 255 = m 2^x, m in [0.5, 1)
+            e = std::min(254, std::max(1, x - 1 + 127));
+        }
+        for (;; ++e) {
+            if (e > 254) return false;
+            const double cell = std::ldexp(1.0, e - 127);
+            bool ok = std::isfinite(wide8_decode(lo, (unsigned char)e, 255));
+            for (int i = 0; i < 8 && ok; ++i) {
+                if (i >= r.n) {   // unused slot: an inverted box (never read: ref = -1)
+                    qlo[a][i] = 255;
+                    qhi[a][i] = 0;
+                    continue;
+                }
+                int ql = (int)std::min(255.0, std::max(0.0, std::floor(((double)r.c[i].lo[a] - lo) / cell)));
+                int qh = (int)std::min(255.0, std::max(0.0, std::ceil(((double)r.c[i].hi[a] - lo) / cell)));
+                // containment is decided by the kernels' own float expression, not by the doubles above
+                while (ql > 0 && wide8_decode(lo, (unsigned char)e, (unsigned char)ql) > r.c[i].lo[a]) --ql;
+                while (qh < 255 && wide8_decode(lo, (unsigned char)e, (unsigned char)qh) < r.c[i].hi[a]) ++qh;
+                ok = wide8_decode(lo, (unsigned char)e, (unsigned char)ql) <= r.c[i].lo[a] &&
+                     wide8_decode(lo, (unsigned char)e, (unsigned char)qh) >= r.c[i].hi[a];
+                qlo[a][i] = (unsigned char)ql;
+                qhi[a][i] = (unsigned char)qh;
+            }
+            if (ok) break;
+        }
+        exp[a] = (unsigned char)e;
+    }
+    return true;
+}
+
 }  // namespace pth

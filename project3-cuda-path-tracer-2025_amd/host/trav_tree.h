@@ -52,4 +52,29 @@ struct QuadRecord {
 void build_quad_records(const std::vector<TravInner>& tree, int bfs_levels, std::vector<QuadRecord>& out,
                         int& stack_need);
 
+// The 8-wide form (pt/pt_bvh_wide.h): record w starts from the two children of one binary inner node
+// and, while it holds fewer than eight children and one of them is inner, replaces the inner child
+// of largest surface area (ties: the first) by that child's own two children.  Numbering, refs and
+// `stack_need` as build_quad_records'.
+struct Wide8Record {
+    TravChild c[8];
+    int n;   // children in use (2..8)
+};
+void build_wide8_records(const std::vector<TravInner>& tree, int bfs_levels, std::vector<Wide8Record>& out,
+                         int& stack_need);
+
+// The quantised boxes of one record: origin = the min corner over the children, one power-of-two
+// cell size per axis as a float's biased exponent (1..254), 8-bit cell indices qlo (rounded down) /
+// qhi (rounded up) such that the DECODED box -- origin + float(q) * 2^(exp - 127), evaluated in float
+// exactly as the kernels do -- contains the child's box; an axis on which every child sits at the
+// origin's coordinate decodes to that coordinate exactly (q = 0).  False: a box is not finite, or
+// no exponent lets 255 cells cover the extent with finite decoded bounds.
+bool quantise_wide8(const Wide8Record& r, float origin[3], unsigned char exp[3], unsigned char qlo[3][8],
+                    unsigned char qhi[3][8]);
+inline float wide8_decode(float origin, unsigned char exp, unsigned char q) {
+    union { unsigned u; float f; } s;
+    s.u = (unsigned)exp << 23;
+    return origin + (float)q * s.f;   // the product is exact (8 bits x a power of two): fused or not, one rounding
+}
+
 }  // namespace pth

@@ -126,6 +126,8 @@ GBUFFER_THROUGH_SYMBOLS = ["pt_gbuffer_capture_through", "pt_gbuffer_get_chain"]
 NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_mesh_tile"]
 # include/pt/pt_geom_bvh.h (primitive intersection through a 4-wide hierarchy over the geoms)
 GEOM_BVH_SYMBOLS = ["pt_set_geom_bvh", "pt_get_geom_bvh", "pt_debug_geom_bvh_info"]
+# include/pt/pt_bvh_wide.h (the traversal kernels on 8-wide quantised records, trees past the L2)
+BVH_WIDE_SYMBOLS = ["pt_set_bvh_wide", "pt_get_bvh_wide", "pt_debug_bvh_wide_info"]
 
 
 def _load():
@@ -177,6 +179,8 @@ def _load():
         "pt_set_naive_mesh": (i32, [i32]), "pt_get_naive_mesh": (i32, [vp, vp]), "pt_debug_naive_mesh_tile": (i32, []),
         "pt_set_geom_bvh": (i32, [i32, i32]), "pt_get_geom_bvh": (i32, [vp, vp, vp]),
         "pt_debug_geom_bvh_info": (i32, [vp, vp, vp]),
+        "pt_set_bvh_wide": (i32, [i32, i32]), "pt_get_bvh_wide": (i32, [vp, vp, vp]),
+        "pt_debug_bvh_wide_info": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -255,6 +259,27 @@ def geom_bvh_info() -> dict:
     n, h, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     _check(lib.pt_debug_geom_bvh_info(ctypes.byref(n), ctypes.byref(h), ctypes.byref(s)), "pt_debug_geom_bvh_info")
     return {"num_nodes": n.value, "height": h.value, "stack_entries": s.value}
+
+
+def set_bvh_wide(enabled: bool, min_refs: int = 0):
+    """The 8-wide quantised record layout for the NEXT pt_init (include/pt/pt_bvh_wide.h): trees of at
+    least `min_refs` refs (<= 0: the default, 65,536) are traversed through it.  Sticky."""
+    _check(lib.pt_set_bvh_wide(int(bool(enabled)), int(min_refs)), "pt_set_bvh_wide")
+
+
+def get_bvh_wide() -> tuple:
+    """(on for the next pt_init, its threshold, the live context's traversal kernels walk the records)."""
+    on, mn, act = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_get_bvh_wide(ctypes.byref(on), ctypes.byref(mn), ctypes.byref(act)), "pt_get_bvh_wide")
+    return bool(on.value), int(mn.value), bool(act.value)
+
+
+def bvh_wide_info() -> dict:
+    """The live context's 8-wide layout (zeros when the mode is not active)."""
+    n, h, s, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_debug_bvh_wide_info(ctypes.byref(n), ctypes.byref(h), ctypes.byref(s), ctypes.byref(b)),
+           "pt_debug_bvh_wide_info")
+    return {"num_records": n.value, "height": h.value, "stack_entries": s.value, "leaf_bytes": b.value}
 
 
 def load_texture(path: str) -> np.ndarray:
@@ -417,17 +442,21 @@ class PathTracer:
 
     _live = None
 
-    def __init__(self, scene, naive_mesh: bool = False, geom_bvh=False, **options):
+    def __init__(self, scene, naive_mesh: bool = False, geom_bvh=False, bvh_wide=False, **options):
         """`naive_mesh=True`: the reference's NAIVE_MESH_LOADING mode for this tracer
         (pt_set_naive_mesh around pt_init; the process-wide setting is put back afterwards).
         `geom_bvh=True | N`: the geom hierarchy of include/pt/pt_geom_bvh.h for this tracer, with the
-        default threshold or for scenes of at least N geoms (set and put back the same way)."""
+        default threshold or for scenes of at least N geoms (set and put back the same way).
+        `bvh_wide=True | N`: the 8-wide quantised records of include/pt/pt_bvh_wide.h, with the default
+        threshold or for trees of at least N refs (set and put back the same way)."""
         if PathTracer._live is not None:
             PathTracer._live.free()       # the library state is process-global, like the reference's
         prev = get_naive_mesh()[0]
         prev_gbvh = get_geom_bvh()[:2]
         set_naive_mesh(naive_mesh)
+        prev_wide = get_bvh_wide()[:2]
         set_geom_bvh(bool(geom_bvh), 0 if isinstance(geom_bvh, bool) else int(geom_bvh))
+        set_bvh_wide(bool(bvh_wide), 0 if isinstance(bvh_wide, bool) else int(bvh_wide))
         try:
             self.opts = default_options(**options)   # after the setter: staged by default in naive mode
             view = scene.view() if hasattr(scene, "view") else scene
@@ -439,6 +468,7 @@ class PathTracer:
         finally:
             set_naive_mesh(prev)
             set_geom_bvh(*prev_gbvh)
+            set_bvh_wide(*prev_wide)
         PathTracer._live = self
         self.iteration = 0
         self._host_image = None
