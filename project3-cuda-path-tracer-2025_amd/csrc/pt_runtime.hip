@@ -46,6 +46,7 @@
 #include "pt/pt_naive_mesh.h"
 #include "pt/pt_geom_bvh.h"
 #include "pt/pt_bvh_wide.h"
+#include "pt/pt_trav_build.h"
 #include "pt_kernels.h"
 #include "pt_denoise_kernels.h"
 #include "pt_gbuffer_through_kernels.h"
@@ -162,9 +163,54 @@ static bool wide_next() {
     return g_wide_next != 0;
 }
 
+// the device build of the SAH hierarchy (pt/pt_trav_build.h): what the next pt_init uses;
+// g_tbuild_next < 0 until first asked, then PT_TRAV_BUILD from the environment or what
+// pt_set_trav_build stored
+constexpr int TBUILD_MIN_LEAVES = 32768;   // from where the device build was not slower (profiles/trav_build_probe.json)
+static int g_tbuild_next = -1, g_tbuild_min = TBUILD_MIN_LEAVES;
+static bool tbuild_next() {
+    if (g_tbuild_next < 0) {
+        const char* e = getenv("PT_TRAV_BUILD");
+        const long v = e ? strtol(e, nullptr, 10) : 0;
+        g_tbuild_next = v >= 1 ? 1 : 0;
+        g_tbuild_min = v > 1 ? (int)std::min<long>(v, 1 << 30) : TBUILD_MIN_LEAVES;
+    }
+    return g_tbuild_next != 0;
+}
+// LayoutParams::sah_builder: the device build from min_leaves leaves, the host's below that and
+// wherever the device build cannot run (no device, an allocation fails); `active` says which it was
+struct TravBuildHook {
+    int min_leaves = 0;
+    bool active = false;
+};
+static bool trav_build_hook(const std::vector<float>& lo, const std::vector<float>& hi, const std::vector<float>& s,
+                            std::vector<pth::TravInner>& out, int& height, int bfs_levels, int max_height, void* user) {
+    TravBuildHook* h = static_cast<TravBuildHook*>(user);
+    bool ok = false;
+    if ((int64_t)s.size() >= h->min_leaves &&
+        pth::build_sah_tree_device(lo, hi, s, out, height, bfs_levels, max_height, ok) == PT_OK) {
+        h->active = ok;
+        return ok;
+    }
+    return pth::build_sah_tree(lo, hi, s, out, height, bfs_levels, max_height);
+}
+
 extern "C" {
 
 int32_t pt_abi_version(void) { return PT_ABI_VERSION; }
+
+int32_t pt_set_trav_build(int32_t on_device, int32_t min_leaves) {
+    g_tbuild_next = on_device ? 1 : 0;
+    g_tbuild_min = min_leaves > 0 ? min_leaves : TBUILD_MIN_LEAVES;
+    return PT_OK;
+}
+int32_t pt_get_trav_build(int32_t* next_on_device, int32_t* next_min, int32_t* active) {
+    const bool on = tbuild_next();
+    if (next_on_device) *next_on_device = on ? 1 : 0;
+    if (next_min) *next_min = g_tbuild_min;
+    if (active) *active = (g_primary.inited && g_primary.trav_build_active) ? 1 : 0;
+    return PT_OK;
+}
 
 int32_t pt_set_bvh_wide(int32_t enabled, int32_t min_refs) {
     g_wide_next = enabled ? 1 : 0;
@@ -373,12 +419,21 @@ static int32_t init_one(const pt_scene_view* s, pt_options o, int share) {
     const bool wide_wanted = wide_next() && !naive && o.shard_mode == PT_SHARD_NONE && o.num_devices <= 1 &&
                              o.pipeline == PT_PIPELINE_FUSED;
     lp.bvh_wide_min = wide_wanted ? g_wide_min : 0;
+    // the SAH hierarchy on this context's device (pt/pt_trav_build.h); the layout calls the hook only
+    // where it would build the tree on the host
+    TravBuildHook tbuild;
+    if (tbuild_next()) {
+        tbuild.min_leaves = g_tbuild_min;
+        lp.sah_builder = trav_build_hook;
+        lp.sah_builder_user = &tbuild;
+    }
     pth::SceneLayout L;
     {
         std::string err;
         const int32_t rc = pth::build_scene_layout(*s, lp, L, err);
         if (rc != PT_OK) return fail(rc, "%s", err.c_str());
     }
+    gp->trav_build_active = tbuild.active;
     o.variant = L.variant;   // minus the near-first traversals, for a tree they cannot walk
     gp->opts.variant = o.variant;
     gp->no_tex = L.no_tex;

@@ -150,6 +150,7 @@ struct State {
     DevLeaf8* d_leaf8 = nullptr;
     bool wide8_active = false;
     int wide8_records = 0, wide8_height = 0, wide8_stack = 0;
+    bool trav_build_active = false;  // the SAH hierarchy came from the device build (pt/pt_trav_build.h)
     float4* d_path[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     float4* d_hit_nt = nullptr;
     int* d_hit_mat = nullptr;

@@ -10,7 +10,10 @@
 //             [--events FILE [--img-dir DIR] [--time-tag TAG]]
 //             [--denoise [LEVELS] [--denoise-through K]] [--denoise-temporal [LEVELS]] [--naive-mesh]
 //             [--denoise-regress [RIDGE]] [--geom-bvh [MIN]] [--bvh-wide [MIN]]
+//             [--trav-build [MIN]]
 //
+// --trav-build builds the SAH hierarchy of mesh trees of at least MIN leaves on the device
+// (include/pt/pt_trav_build.h): the host's tree bit for bit, so the same image; pt_init is shorter.
 // --bvh-wide walks mesh trees of at least MIN refs as 8-wide quantised records (include/pt/pt_bvh_wide.h)
 // --geom-bvh traces the cubes and spheres through a 4-wide hierarchy over them (include/pt/pt_geom_bvh.h)
 // in scenes of at least MIN geoms (default 65): same image, for scenes of many primitives.
@@ -53,6 +56,7 @@
 #include "image_io.h"
 #include "pathtrace.h"
 #include "pt/pt_bvh_wide.h"
+#include "pt/pt_trav_build.h"
 #include "pt/pt_denoise.h"
 #include "pt/pt_denoise_regress.h"
 #include "pt/pt_denoise_temporal.h"
@@ -187,13 +191,14 @@ int main(int argc, char** argv) {
                     "[--devices N|K0,K1,... [--combine peer|rccl]] "
                     "[--events FILE [--img-dir DIR] [--time-tag TAG]] [--denoise [LEVELS] [--denoise-through K]] "
                     "[--denoise-temporal [LEVELS]] [--naive-mesh] [--denoise-regress [RIDGE]] [--geom-bvh [MIN]] "
-                    "[--bvh-wide [MIN]]\n", argv[0]);
+                    "[--bvh-wide [MIN]] [--trav-build [MIN]]\n", argv[0]);
         return 1;
     }
     std::string scene_file = argv[1], out, events, img_dir = "../img", time_tag;
     bool gpu_bvh = false, naive_mesh = false;
     int geom_bvh_min = -1;    // -1: no --geom-bvh; 0: its default threshold
     int bvh_wide_min = -1;    // the same for --bvh-wide
+    int trav_build_min = -1;  // the same for --trav-build
     int spp = -1, resx = 0, resy = 0, depth = -1;
     int denoise_levels = 0;   // 0: no --denoise
     int temporal_levels = 0;  // 0: no --denoise-temporal
@@ -218,8 +223,8 @@ int main(int argc, char** argv) {
         else if (a == "--device") opts.device = std::atoi(next());
         else if (a == "--gpu-bvh") gpu_bvh = true;
         else if (a == "--naive-mesh") naive_mesh = true;
-        else if (a == "--geom-bvh" || a == "--bvh-wide") {   // the threshold is optional, like --denoise's level count
-            int& min = a == "--geom-bvh" ? geom_bvh_min : bvh_wide_min;
+        else if (a == "--geom-bvh" || a == "--bvh-wide" || a == "--trav-build") {   // the threshold is optional, like --denoise's level count
+            int& min = a == "--geom-bvh" ? geom_bvh_min : a == "--bvh-wide" ? bvh_wide_min : trav_build_min;
             min = 0;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
                 const char* v = argv[++i];
@@ -302,6 +307,7 @@ int main(int argc, char** argv) {
     }
     if (geom_bvh_min >= 0) pathtraceSetGeomBvh(true, geom_bvh_min);
     if (bvh_wide_min >= 0) pt_set_bvh_wide(1, bvh_wide_min);
+    if (trav_build_min >= 0) pt_set_trav_build(1, trav_build_min);
     if (naive_mesh) {   // the mode runs on the staged pipeline
         pathtraceSetNaiveMesh(true);
         opts.pipeline = PT_PIPELINE_STAGED;

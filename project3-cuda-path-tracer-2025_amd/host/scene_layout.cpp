@@ -581,7 +581,9 @@ bool build_sah_hierarchy(const RefTree& rt, const LayoutParams& p, const SceneLa
         lhi[3 * k] = nd.hi.x; lhi[3 * k + 1] = nd.hi.y; lhi[3 * k + 2] = nd.hi.z;
         ls[k] = out.node_aux[rt.leaf_nodes[k]].y;
     }
-    bool sah = build_sah_tree(llo, lhi, ls, tt, th, p.bvh_bfs_levels, p.sah_max_height) && th + 1 <= MAXSTACK &&
+    bool sah = (p.sah_builder ? p.sah_builder(llo, lhi, ls, tt, th, p.bvh_bfs_levels, p.sah_max_height, p.sah_builder_user)
+                              : build_sah_tree(llo, lhi, ls, tt, th, p.bvh_bfs_levels, p.sah_max_height)) &&
+               th + 1 <= MAXSTACK &&
                (int64_t)tt.size() + L < (1 << 24);
     if (sah) {   // the union of the leaves is the reference root box, bit for bit
         const TravChild& a = tt[0].c[0];

@@ -14,6 +14,7 @@
 #include "pt/pathtrace_abi.h"
 #include "geom_bvh.h"
 #include "pt_records.h"
+#include "trav_tree.h"
 
 namespace pth {
 
@@ -38,6 +39,10 @@ struct LayoutParams {
     // the 8-wide quantised records (pt/pt_bvh_wide.h): built beside the pairs for SAH trees of at
     // least bvh_wide_min refs (0: the mode is off)
     int bvh_wide_min = 0;
+    // builds the SAH hierarchy in build_sah_tree's place when set (pt/pt_trav_build.h: the runtime
+    // installs the device build here; this code stays host-only)
+    SahTreeBuilder sah_builder = nullptr;
+    void* sah_builder_user = nullptr;
 };
 
 struct SceneLayout {

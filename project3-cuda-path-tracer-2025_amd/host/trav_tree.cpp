@@ -59,8 +59,8 @@ bool build_sah_tree(const std::vector<float>& leaf_lo, const std::vector<float>&
 
     std::vector<int> idx(n);
     std::iota(idx.begin(), idx.end(), 0);
-    std::vector<Tmp> T;
-    T.reserve(n);
+    std::vector<int> kids(2 * (size_t)(n - 1), 0);   // the tree's shape in preorder (finish_sah_tree)
+    int made = 0;
     struct Work {
         int begin, end, parent, side, depth;
     };
@@ -72,7 +72,6 @@ bool build_sah_tree(const std::vector<float>& leaf_lo, const std::vector<float>&
         int code;
         if (w.end - w.begin == 1) {
             code = -(idx[w.begin] + 1);
-            height = std::max(height, w.depth);
         } else {
             // centroid bounds
             double cl[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, ch[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
@@ -141,12 +140,28 @@ bool build_sah_tree(const std::vector<float>& leaf_lo, const std::vector<float>&
                     return cx < cy || (cx == cy && x < y);
                 });
             }
-            code = (int)T.size();
-            T.push_back(Tmp{});
+            code = made++;
             st.push_back({mid, w.end, code, 1, w.depth + 1});
             st.push_back({w.begin, mid, code, 0, w.depth + 1});
         }
-        if (w.parent >= 0) T[w.parent].kid[w.side] = code;
+        if (w.parent >= 0) kids[2 * (size_t)w.parent + w.side] = code;
+    }
+    finish_sah_tree(kids, leaf_lo, leaf_hi, leaf_s, out, height, bfs_levels);
+    return true;
+}
+
+void finish_sah_tree(const std::vector<int>& kids, const std::vector<float>& leaf_lo, const std::vector<float>& leaf_hi,
+                     const std::vector<float>& leaf_s, std::vector<TravInner>& out, int& height, int bfs_levels) {
+    std::vector<Tmp> T(kids.size() / 2);
+    height = 0;
+    {   // levels: a parent precedes its children; a leaf child of a node on level d is on level d + 1
+        std::vector<int> lvl(T.size(), 1);
+        for (size_t i = 0; i < T.size(); ++i)
+            for (int c = 0; c < 2; ++c) {
+                const int k = T[i].kid[c] = kids[2 * i + c];
+                if (k >= 0) lvl[k] = lvl[i] + 1;
+                else height = std::max(height, lvl[i] + 1);
+            }
     }
     // boxes and cull sizes bottom-up (children are created after their parent)
     auto child_box = [&](int code, float* lo, float* hi, float& s) {
@@ -217,7 +232,6 @@ bool build_sah_tree(const std::vector<float>& leaf_lo, const std::vector<float>&
             ch.ref = ch.leaf ? -t.kid[c] - 1 : bfs[t.kid[c]];
         }
     }
-    return true;
 }
 
 void build_quad_records(const std::vector<TravInner>& tt, int bfs_levels, std::vector<QuadRecord>& out,

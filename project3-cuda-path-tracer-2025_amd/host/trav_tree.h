@@ -39,6 +39,25 @@ bool build_sah_tree(const std::vector<float>& leaf_lo, const std::vector<float>&
                     const std::vector<float>& leaf_s, std::vector<TravInner>& out, int& height,
                     int bfs_levels = 1 << 30, int max_height = 1 << 30);
 
+// The second half of build_sah_tree, shared with the device build (csrc/pt_trav_build.hip): from the
+// tree's shape alone -- inner node i's children kids[2 i], kids[2 i + 1] (>= 0: an inner node, < 0:
+// -(leaf + 1)), the nodes in depth-first preorder (left child = parent + 1, right child = parent +
+// the left child's leaf count) -- the boxes and cull sizes bottom-up (the left child wins a tie, which
+// decides the sign of a zero bound), `height`, and the records in their final numbering.
+void finish_sah_tree(const std::vector<int>& kids, const std::vector<float>& leaf_lo, const std::vector<float>& leaf_hi,
+                     const std::vector<float>& leaf_s, std::vector<TravInner>& out, int& height, int bfs_levels);
+
+// A replacement for build_sah_tree (same arguments and contract, plus a user pointer): what
+// LayoutParams::sah_builder holds.  build_sah_tree_device is the one the runtime installs
+// (pt/pt_trav_build.h); it is defined in csrc/pt_trav_build.hip, so only the HIP library links it.
+using SahTreeBuilder = bool (*)(const std::vector<float>& leaf_lo, const std::vector<float>& leaf_hi,
+                                const std::vector<float>& leaf_s, std::vector<TravInner>& out, int& height,
+                                int bfs_levels, int max_height, void* user);
+// 0: built (`ok` as build_sah_tree returns it); otherwise a PT_E_* code, with nothing built
+int build_sah_tree_device(const std::vector<float>& leaf_lo, const std::vector<float>& leaf_hi,
+                          const std::vector<float>& leaf_s, std::vector<TravInner>& out, int& height, int bfs_levels,
+                          int max_height, bool& ok);
+
 // The 4-wide form of a tree from build_sah_tree: record q holds the children of one binary inner
 // node, an inner child replaced by its own two children (two levels per record: 2 to 4 children).
 // Record 0 is the root's.  Records are numbered breadth-first over the top `bfs_levels` levels and

@@ -128,6 +128,11 @@ NAIVE_MESH_SYMBOLS = ["pt_set_naive_mesh", "pt_get_naive_mesh", "pt_debug_naive_
 GEOM_BVH_SYMBOLS = ["pt_set_geom_bvh", "pt_get_geom_bvh", "pt_debug_geom_bvh_info"]
 # include/pt/pt_bvh_wide.h (the traversal kernels on 8-wide quantised records, trees past the L2)
 BVH_WIDE_SYMBOLS = ["pt_set_bvh_wide", "pt_get_bvh_wide", "pt_debug_bvh_wide_info"]
+# include/pt/pt_trav_build.h (the SAH traversal hierarchy built on the device, the host's tree bit for bit)
+TRAV_BUILD_SYMBOLS = ["pt_set_trav_build", "pt_get_trav_build", "pt_trav_build", "pt_trav_build_last_error"]
+TRAV_BUILD_PIECE, TRAV_BUILD_SUBTREE = 2048, 1024   # PT_TRAV_BUILD_PIECE / PT_TRAV_BUILD_SUBTREE
+TRAV_CHILD = np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3), ("ref", "<i4"), ("leaf", "<i4"), ("s", "<f4")])
+TRAV_INNER = np.dtype([("c", TRAV_CHILD, 2)])        # pt_trav_inner, 72 bytes
 
 
 def _load():
@@ -181,6 +186,9 @@ def _load():
         "pt_debug_geom_bvh_info": (i32, [vp, vp, vp]),
         "pt_set_bvh_wide": (i32, [i32, i32]), "pt_get_bvh_wide": (i32, [vp, vp, vp]),
         "pt_debug_bvh_wide_info": (i32, [vp, vp, vp, vp]),
+        "pt_set_trav_build": (i32, [i32, i32]), "pt_get_trav_build": (i32, [vp, vp, vp]),
+        "pt_trav_build": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
+        "pt_trav_build_last_error": (ctypes.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -280,6 +288,41 @@ def bvh_wide_info() -> dict:
     _check(lib.pt_debug_bvh_wide_info(ctypes.byref(n), ctypes.byref(h), ctypes.byref(s), ctypes.byref(b)),
            "pt_debug_bvh_wide_info")
     return {"num_records": n.value, "height": h.value, "stack_entries": s.value, "leaf_bytes": b.value}
+
+
+def set_trav_build(on_device: bool, min_leaves: int = 0):
+    """Where the NEXT pt_init builds the SAH traversal hierarchy (include/pt/pt_trav_build.h): on the
+    device for trees of at least `min_leaves` leaves (<= 0: the default, 32,768), else on the host.  Sticky."""
+    _check(lib.pt_set_trav_build(int(bool(on_device)), int(min_leaves)), "pt_set_trav_build")
+
+
+def get_trav_build() -> tuple:
+    """(device build on for the next pt_init, its threshold, the live context's tree came from it)."""
+    on, mn, act = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib.pt_get_trav_build(ctypes.byref(on), ctypes.byref(mn), ctypes.byref(act)), "pt_get_trav_build")
+    return bool(on.value), int(mn.value), bool(act.value)
+
+
+def trav_build(lo, hi, s, where: str = "host", bfs_levels: int = 12, max_height: int = 1 << 30):
+    """pt_trav_build: the binned-SAH hierarchy over leaf boxes lo / hi (n, 3) with cull sizes s (n,),
+    built on the host or (where="gpu") on the current device: (TRAV_INNER array, height).  A
+    PtError carries the code (PtError.code) of a rejected input."""
+    lo = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+    s = np.ascontiguousarray(s, np.float32).reshape(-1)
+    n = len(s)
+    if len(lo) != n or len(hi) != n:
+        raise ValueError("lo, hi and s must describe the same number of leaves")
+    out = np.zeros(max(1, n - 1), TRAV_INNER)
+    cnt, height = ctypes.c_int32(), ctypes.c_int32()
+    rc = lib.pt_trav_build(_ptr(lo), _ptr(hi), _ptr(s), n, int(bfs_levels), int(max_height),
+                           {"host": 0, "gpu": 1}[where], out.ctypes.data, len(out), ctypes.byref(cnt),
+                           ctypes.byref(height))
+    if rc != PT_OK:
+        e = PtError(f"pt_trav_build: {lib.pt_trav_build_last_error().decode(errors='replace')} (code {rc})")
+        e.code = rc
+        raise e
+    return out[:cnt.value].copy(), int(height.value)
 
 
 def load_texture(path: str) -> np.ndarray:
@@ -442,13 +485,15 @@ class PathTracer:
 
     _live = None
 
-    def __init__(self, scene, naive_mesh: bool = False, geom_bvh=False, bvh_wide=False, **options):
+    def __init__(self, scene, naive_mesh: bool = False, geom_bvh=False, bvh_wide=False, trav_build=False, **options):
         """`naive_mesh=True`: the reference's NAIVE_MESH_LOADING mode for this tracer
         (pt_set_naive_mesh around pt_init; the process-wide setting is put back afterwards).
         `geom_bvh=True | N`: the geom hierarchy of include/pt/pt_geom_bvh.h for this tracer, with the
         default threshold or for scenes of at least N geoms (set and put back the same way).
         `bvh_wide=True | N`: the 8-wide quantised records of include/pt/pt_bvh_wide.h, with the default
-        threshold or for trees of at least N refs (set and put back the same way)."""
+        threshold or for trees of at least N refs (set and put back the same way).
+        `trav_build=True | N`: the SAH hierarchy built on the device (include/pt/pt_trav_build.h), with
+        the default threshold or for trees of at least N leaves (set and put back the same way)."""
         if PathTracer._live is not None:
             PathTracer._live.free()       # the library state is process-global, like the reference's
         prev = get_naive_mesh()[0]
@@ -457,6 +502,8 @@ class PathTracer:
         prev_wide = get_bvh_wide()[:2]
         set_geom_bvh(bool(geom_bvh), 0 if isinstance(geom_bvh, bool) else int(geom_bvh))
         set_bvh_wide(bool(bvh_wide), 0 if isinstance(bvh_wide, bool) else int(bvh_wide))
+        prev_tbuild = get_trav_build()[:2]
+        set_trav_build(bool(trav_build), 0 if isinstance(trav_build, bool) else int(trav_build))
         try:
             self.opts = default_options(**options)   # after the setter: staged by default in naive mode
             view = scene.view() if hasattr(scene, "view") else scene
@@ -469,6 +516,7 @@ class PathTracer:
             set_naive_mesh(prev)
             set_geom_bvh(*prev_gbvh)
             set_bvh_wide(*prev_wide)
+            set_trav_build(*prev_tbuild)
         PathTracer._live = self
         self.iteration = 0
         self._host_image = None
